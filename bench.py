@@ -34,7 +34,10 @@ mean) of the fittest individual of the last completed generation (fitness
 itself is the reference's binary accuracy).
 
 Run: ``python bench.py --gpus 1 --steps 2 --warmup 1`` or, for N>1,
-``torchrun --nproc-per-node N bench.py --gpus N ...``.
+``torchrun --nproc-per-node N bench.py --gpus N ...``. A plain run does only
+what the headline figure needs; ``--dump-outputs DIR`` also writes the scores
+of the last timed round as ``.npy`` files, ``--full`` is reserved for
+measurements beyond the headline.
 """
 
 import argparse
@@ -104,7 +107,47 @@ def parse():
     ap.add_argument("--pad-images", type=int, default=1,
                     help="1: a 28x28 image is stored zero-padded to 32x32 so every stage runs the "
                          "shape-specialised kernels (ops/cnn_kernels.padded_hw); 0: the generic kernels")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed round returned to its caller as "
+                         "DIR/<name>.npy (see dump_outputs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the measurements that are not needed for the headline figure. There are none "
+                         "yet: a plain run sets up, warms up, times the steps and reports, and every other "
+                         "figure of the project comes from a tool of its own under tools/; a measurement added "
+                         "to this file later belongs behind this flag")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
+
+
+def dump_outputs(dirname, evaluated, nfold):
+    """What the last timed round handed back to the GA, one row per candidate in dispatch order, as
+    ``<dirname>/<name>.npy``: ``genes`` (the genome bits, stages concatenated in name order, float32),
+    ``fitness`` (mean binary validation accuracy), ``fold_scores`` (binary validation accuracy per fold) and
+    ``categorical_accuracy`` (per fold), float64. A candidate whose evaluation failed has NaN fold rows.
+    Data, folds, initial population and weight seeds follow from the arguments alone, so two runs with the
+    same arguments evaluate the same candidates on the same inputs."""
+    import numpy as np
+
+    def folds(values):
+        row = np.full(nfold, np.nan, np.float64)
+        if values is not None:
+            row[:len(values)] = values
+        return row
+
+    genes = [ind.get_genes() for ind in evaluated]
+    arrays = {
+        "genes": np.array([[float(b) for name in sorted(g) for b in g[name]] for g in genes], np.float32),
+        "fitness": np.array([ind.get_fitness() for ind in evaluated], np.float64),
+        "fold_scores": np.array([folds(getattr(ind, "fold_scores", None)) for ind in evaluated], np.float64),
+        "categorical_accuracy": np.array(
+            [folds((getattr(ind, "fold_metrics", None) or {}).get("categorical_accuracy")) for ind in evaluated],
+            np.float64),
+    }
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
 
 
 def main():
@@ -231,6 +274,7 @@ def run(args):
         ga.generation += 1
 
     best_seen = {}          # fittest individual evaluated so far (any generation, complete or not)
+    last_round = []         # the individuals the latest round evaluated (--dump-outputs)
 
     def track():
         for ind in ga.population:
@@ -245,7 +289,9 @@ def run(args):
         if not ga.population.pending():
             advance()
         ga.population.ga_generation = ga.generation
+        todo = ga.population.pending()           # evaluate_round takes the first n of these
         n = ga.population.evaluate_round(per_gpu, slack=slack)
+        last_round[:] = todo[:n]
         track()
         return n
 
@@ -267,6 +313,8 @@ def run(args):
             ga.population.last_dispatch), file=sys.stderr, flush=True)
     ga.population.sync_ranks()
     elapsed = time.perf_counter() - t_start
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, last_round, args.nfold)
     if not ga.population.pending():
         advance()                                # close the generation the last round finished
     ga.population.shutdown()

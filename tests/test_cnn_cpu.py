@@ -98,6 +98,32 @@ def test_bench_contract_cpu():
     assert rec["n_gpus"] == 1 and rec["value"] > 0 and rec["higher_is_better"] is True
 
 
+def test_bench_dump_outputs_cpu(tmp_path):
+    """--dump-outputs writes the last timed round's scores as float .npy files, --steps sets the number
+    of timed rounds, and a second run with the same arguments reproduces the arrays exactly."""
+    env = dict(os.environ, PYTHONPATH=ROOT)
+    recs = []
+    for d in ("a", "b"):
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1",
+                              "--per-gpu", "1", "--population", "8", "--epochs", "1", "--lr", "1e-3", "--samples",
+                              "120", "--nfold", "2", "--backend", "torch", "--full", "--dump-outputs",
+                              str(tmp_path / d)], capture_output=True, text=True, env=env, timeout=600, cwd=ROOT)
+        assert out.returncode == 0, out.stderr[-2000:]
+        recs.append(json.loads(out.stdout))
+    rec = recs[0]
+    assert rec["steps"] == 2 and len(rec["config"]["rounds"]) == 2
+    assert abs(rec["ms_per_step"] - 1000.0 * rec["elapsed_s"] / 2) < 0.3      # elapsed_s is rounded to 1 ms
+    n = rec["config"]["rounds"][-1]
+    shapes = {"genes": (n, 13), "fitness": (n,), "fold_scores": (n, 2), "categorical_accuracy": (n, 2)}
+    assert sorted(os.listdir(tmp_path / "a")) == sorted(k + ".npy" for k in shapes)
+    for name, shape in shapes.items():
+        a = np.load(tmp_path / "a" / (name + ".npy"))
+        assert a.shape == shape and a.dtype in (np.float32, np.float64) and np.isfinite(a).all(), name
+        assert np.array_equal(a, np.load(tmp_path / "b" / (name + ".npy"))), name
+    a = {k: np.load(tmp_path / "a" / (k + ".npy")) for k in shapes}
+    assert np.allclose(a["fitness"], a["fold_scores"].mean(1)) and set(np.unique(a["genes"])) <= {0.0, 1.0}
+
+
 def test_sgd_momentum_update_rule():
     """One Keras-SGD step: v = mu v - lr g ; p += v (velocity reset per lr stage)."""
     x, y = _data(64)
