@@ -4,6 +4,13 @@
 #pragma once
 #include "common.h"
 
+// dynamic LDS above 64 KiB: raise the per-function limit (gfx950 has 160 KiB per CU)
+template <typename F>
+static void lds_limit(F* fn, size_t bytes) {
+  if (bytes > 65536) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                         (int)bytes);
+}
+
 // Population batching: a launch covers the "groups" (candidate x fold
 // replicas) listed in a group table. Activations / gradients live in SLOT
 // tensors [Q][B][H][W][C] (Q = all groups of the job); a group's record says

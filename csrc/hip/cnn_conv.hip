@@ -642,12 +642,6 @@ extern "C" int gt_wgrad_fast(const WgradArgs* a, hipStream_t stream);
 static int g_conv_fast = 1;   // shape-specialised kernels (cnn_conv_fast.hip) where one matches
 static int g_conv_imgs = 2;   // max whole small images per generic-conv workgroup (2: measured best, deep space)
 
-template <typename F>
-static void set_lds_limit(F* fn, size_t bytes) {
-  if (bytes > 65536) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                         (int)bytes);
-}
-
 template <int PREC>
 static int conv_fwd_generic(const ConvArgs* a, hipStream_t stream) {
   constexpr int NPL = PREC ? GT_NPL_F32 : 1;
@@ -691,13 +685,13 @@ static int conv_fwd_generic(const ConvArgs* a, hipStream_t stream) {
                    4 * ((size_t)a->KH * a->KW * t.cbb + 4);
   dim3 grid(((a->B + ni - 1) / ni) * nth, a->ngroups, (a->Coutp + 63) / 64);
   if (tile > 128) {
-    set_lds_limit(conv_fwd_kernel<4, PREC>, lds);
+    lds_limit(conv_fwd_kernel<4, PREC>, lds);
     hipLaunchKernelGGL((conv_fwd_kernel<4, PREC>), grid, dim3(256), lds, stream, t);
   } else if (tile > 64) {
-    set_lds_limit(conv_fwd_kernel<2, PREC>, lds);
+    lds_limit(conv_fwd_kernel<2, PREC>, lds);
     hipLaunchKernelGGL((conv_fwd_kernel<2, PREC>), grid, dim3(256), lds, stream, t);
   } else {
-    set_lds_limit(conv_fwd_kernel<1, PREC>, lds);
+    lds_limit(conv_fwd_kernel<1, PREC>, lds);
     hipLaunchKernelGGL((conv_fwd_kernel<1, PREC>), grid, dim3(256), lds, stream, t);
   }
   return (int)hipGetLastError();

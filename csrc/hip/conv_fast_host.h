@@ -1,156 +1,141 @@
-// Host-side dispatch helpers of the shape-specialised conv / wgrad kernels (conv_fast_impl.h), shared by
-// cnn_conv_fast.hip and cnn_conv_fast_ext.hip. The launch macros expect, in the including translation
-// unit: g_probe (probe mode: report the tile rows instead of launching), regepi_on(), smallq_th(),
-// g_wgrad_nb and wgrad_nz().
+// Host-side dispatch data of the shape-specialised conv / wgrad kernels (conv_fast_impl.h), shared by
+// cnn_conv_fast.hip and cnn_conv_fast_ext.hip: a descriptor per kernel instantiation (built by ONE function
+// template from the template arguments, so its numbers and its kernel address cannot disagree), the row types
+// of the two shape tables and the switches. Selection and launch (select_conv / select_wgrad) are in
+// cnn_conv_fast.hip; cnn_conv_fast_ext.hip only contributes rows.
 #pragma once
+#include <initializer_list>
+#include <vector>
+
 #include "conv_fast_impl.h"
 
-// dynamic LDS above 64 KiB: raise the per-function limit once (gfx950 has 160 KiB per CU)
-template <typename F>
-static void lds_limit(F* fn, size_t bytes) {
-  if (bytes > 65536) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                         (int)bytes);
+// ---------------------------------------------------------------------------
+// switches (tests compare variants through the gt_*_set_* entry points of cnn_conv_fast.hip)
+// ---------------------------------------------------------------------------
+struct FastSwitches {
+  int s2in_ct1 = 1;      // one co tile per wave for the S=(3,5) s2 input-conv dgrad (gt_conv_set_s2in_ct1)
+  int regepi = 1;        // fp32 register-direct epilogue of the tile kernel (gt_conv_set_regepi)
+  int smallq = 1;        // shorter tiles for small launches (gt_conv_set_smallq) ...
+  long smallq_wg = 300;  // ... while the grid is below this many workgroups
+  int wgrad_nb = 0;      // 0: per-shape default, 1 / 2: force band buffers (gt_wgrad_set_nb)
+  int wgrad_nz = 0;      // 0: automatic column slices, 1 / 2 / 4 / 8 forced (gt_wgrad_set_nz)
+};
+extern FastSwitches g_fast;   // cnn_conv_fast.hip
+
+// ---------------------------------------------------------------------------
+// conv: descriptor, variants, rows
+// ---------------------------------------------------------------------------
+// one conv_fast_kernel instantiation
+struct ConvKernel {
+  int KH, KW, NCBI, W, TH, NT, NCO, NWV, PREC, PK, RE, CTX, SCH;
+  int lds_fwd, lds_bwd;   // FastCfg::lds of forward (epi_bf16) and other launches
+  const void* fn;
+};
+
+template <int KH, int KW, int NCBI, int W, int TH, int NT, int NCO, int NWV, int PREC, int PK = 0, int RE = 0,
+          int CTX = 0, int SCH = 0>
+static ConvKernel conv_kernel() {
+  static_assert((NCO * 8 + 15) / 16 == NT, "NT co tiles of 16 cover the NCO chunks of 8 channels");
+  using Cfg = FastCfg<KH, KW, NCBI, W, TH, NT, NCO, PREC>;
+  return {KH, KW, NCBI, W, TH, NT, NCO, NWV, PREC, PK, RE, CTX, SCH, (int)Cfg::lds(true), (int)Cfg::lds(false),
+          reinterpret_cast<const void*>(&conv_fast_kernel<KH, KW, NCBI, W, TH, NT, NCO, NWV, PREC, PK, RE, CTX, SCH>)};
 }
 
-#define CONV_FAST_LAUNCH_PK(KH_, KW_, NCBI_, W_, TH_, NT_, NCO_, NWV_, PREC_, PK_)                        \
-  {                                                                                                     \
-    if (g_probe) return 1000 + TH_;                                                                     \
-    dim3 grid(a->B * (a->H / TH_), a->ngroups);                                                         \
-    const size_t lds = FastCfg<KH_, KW_, NCBI_, W_, TH_, NT_, NCO_, PREC_>::lds(a->epi_bf16 != 0);      \
-    auto* fn = conv_fast_kernel<KH_, KW_, NCBI_, W_, TH_, NT_, NCO_, NWV_, PREC_, PK_>;                 \
-    if (PREC_ == 1 && (W_ % 16) == 0 && regepi_on())                                                    \
-      fn = conv_fast_kernel<KH_, KW_, NCBI_, W_, TH_, NT_, NCO_, NWV_, PREC_, PK_, 1>;                  \
-    lds_limit(fn, lds);                                                                                 \
-    hipLaunchKernelGGL(fn, grid, dim3(NWV_ * 64), lds, stream, *a);                                     \
-    return (int)hipGetLastError();                                                                      \
-  }
-#define CONV_FAST_LAUNCH(KH_, KW_, NCBI_, W_, TH_, NT_, NCO_, NWV_, PREC_)                               \
-  CONV_FAST_LAUNCH_PK(KH_, KW_, NCBI_, W_, TH_, NT_, NCO_, NWV_, PREC_, 0)
+// conditions of a variant (all must hold)
+enum : int {
+  IF_TH = 1,     // the small-launch rule (smallq_th) returns this variant's tile rows
+  IF_PK = 2,     // the packed last co tile applies (pk_ok)
+  IF_RE = 4,     // register-epilogue switch on
+  IF_S2CT1 = 8,  // s2in_ct1 switch on
+};
+
+struct ConvVariant {
+  int cond;
+  ConvKernel k;
+};
+typedef std::vector<ConvVariant> ConvVariants;
+
+// the tile kernel (a wave owns CT <= 2 co tiles x PG pixel groups). fp32 images 16 / 32 wide: its
+// register-epilogue twin first, taken while that switch is on. (A plain `if`: the twin is compiled for the
+// other shapes too, never run, exactly as the launch macros did -- the set of kernels in the library is unchanged.)
+template <int KH, int KW, int NCBI, int W, int TH, int NT, int NCO, int NWV, int PREC, int PK = 0>
+static ConvVariants tile(int cond = 0) {
+  ConvVariants v;
+  if (PREC == 1 && W % 16 == 0) v.push_back({cond | IF_RE, conv_kernel<KH, KW, NCBI, W, TH, NT, NCO, NWV, PREC, PK, 1>()});
+  v.push_back({cond, conv_kernel<KH, KW, NCBI, W, TH, NT, NCO, NWV, PREC, PK, 0>()});
+  return v;
+}
 
 // one co tile per wave (CTX 1), fp32, register-direct epilogue
-#define CONV_FAST_LAUNCH_CT1(KH_, KW_, NCBI_, W_, TH_, NT_, NCO_, NWV_) \
-  CONV_FAST_LAUNCH_CT1S(KH_, KW_, NCBI_, W_, TH_, NT_, NCO_, NWV_, 1)
-#define CONV_FAST_LAUNCH_CT1S(KH_, KW_, NCBI_, W_, TH_, NT_, NCO_, NWV_, SCH_)                            \
-  {                                                                                                     \
-    if (g_probe) return 1000 + TH_;                                                                     \
-    dim3 grid(a->B * (a->H / TH_), a->ngroups);                                                         \
-    const size_t lds = FastCfg<KH_, KW_, NCBI_, W_, TH_, NT_, NCO_, 1>::lds(a->epi_bf16 != 0);          \
-    auto* fn = conv_fast_kernel<KH_, KW_, NCBI_, W_, TH_, NT_, NCO_, NWV_, 1, 0, 1, 1, SCH_>;           \
-    lds_limit(fn, lds);                                                                                 \
-    hipLaunchKernelGGL(fn, grid, dim3(NWV_ * 64), lds, stream, *a);                                     \
-    return (int)hipGetLastError();                                                                      \
-  }
-
-// the packed last co tile applies: fp32, the real output channels leave <= 4 in the last 16-channel tile
-static bool pk_ok(const ConvArgs* a, int nt) {
-  const int last = a->cout_real - 16 * (nt - 1);
-  return a->prec == 1 && a->cout_real > 0 && last >= 1 && last <= 4;
+template <int KH, int KW, int NCBI, int W, int TH, int NT, int NCO, int NWV, int SCH = 1>
+static ConvVariants ct1(int cond = 0) {
+  return {{cond, conv_kernel<KH, KW, NCBI, W, TH, NT, NCO, NWV, 1, 0, 1, 1, SCH>()}};
 }
 
-#define CONV_FAST_MATCH(KH_, KW_, NCBI_, W_, TH_, NT_, NCO_)                                             \
-  (a->KH == KH_ && a->KW == KW_ && a->Cinp == NCBI_ * 8 && a->W == W_ && a->Coutp == NCO_ * 8 &&       \
-   (NCO_ * 8 + 15) / 16 == NT_ && a->H % TH_ == 0)
-
-#define CONV_FAST_CASE(KH_, KW_, NCBI_, W_, TH_, NT_, NCO_)                                              \
-  if (CONV_FAST_MATCH(KH_, KW_, NCBI_, W_, TH_, NT_, NCO_)) CONV_FAST_LAUNCH(KH_, KW_, NCBI_, W_, TH_, NT_, NCO_, 4, 0)
-
-// shapes with an 8-wave instantiation: `def_` waves unless overridden
-#define CONV_FAST_CASE2(KH_, KW_, NCBI_, W_, TH_, NT_, NCO_, def_)                                       \
-  if (CONV_FAST_MATCH(KH_, KW_, NCBI_, W_, TH_, NT_, NCO_)) {                                           \
-    if ((g_conv_nwv ? g_conv_nwv : def_) == 8) CONV_FAST_LAUNCH(KH_, KW_, NCBI_, W_, TH_, NT_, NCO_, 8, 0) \
-    CONV_FAST_LAUNCH(KH_, KW_, NCBI_, W_, TH_, NT_, NCO_, 4, 0)                                         \
+// One geometry (KH, KW, Cinp / 8, W, Coutp / 8, prec: those of its kernels) with H % hmod == 0. The first
+// variant whose conditions hold runs. The small-launch rule halves the tile from hmod rows down to thmin
+// (thmin == hmod: none).
+struct ConvRow {
+  int hmod, thmin;
+  ConvVariants v;
+  ConvRow(int hmod_, int thmin_, std::initializer_list<ConvVariants> parts) : hmod(hmod_), thmin(thmin_) {
+    for (const ConvVariants& p : parts) v.insert(v.end(), p.begin(), p.end());
   }
+};
 
-// odd tile counts (104 channels = 7 x 16): one co tile per wave, NT waves
-#define CONV_FAST_CASE_NW(KH_, KW_, NCBI_, W_, TH_, NT_, NCO_, NWV_)                                      \
-  if (CONV_FAST_MATCH(KH_, KW_, NCBI_, W_, TH_, NT_, NCO_)) CONV_FAST_LAUNCH(KH_, KW_, NCBI_, W_, TH_, NT_, NCO_, NWV_, 0)
+// ---------------------------------------------------------------------------
+// wgrad: descriptor and rows
+// ---------------------------------------------------------------------------
+// one wgrad_fast_kernel (PREC 0) / wgrad_fast_f32_kernel (PREC 1) instantiation
+struct WgradKernel {
+  int KH, KW, NCBI, NCBO, W, R, NW, NB, PK, NZ, PREC;
+  const void* fn;
+};
 
-#define CONV_FAST_CASE_F32(KH_, KW_, NCBI_, W_, TH_, NT_, NCO_, NWV_)                                     \
-  if (CONV_FAST_MATCH(KH_, KW_, NCBI_, W_, TH_, NT_, NCO_)) {                                           \
-    CONV_FAST_LAUNCH(KH_, KW_, NCBI_, W_, TH_, NT_, NCO_, NWV_, 1)                                      \
-  }
-// narrow images (W < 16: no persistent variant), and the wide deep-space shapes (tile kernel only)
-#define CONV_FAST_CASE_F32_NARROW(KH_, KW_, NCBI_, W_, TH_, NT_, NCO_, NWV_)                              \
-  if (CONV_FAST_MATCH(KH_, KW_, NCBI_, W_, TH_, NT_, NCO_)) CONV_FAST_LAUNCH(KH_, KW_, NCBI_, W_, TH_, NT_, NCO_, NWV_, 1)
-// shapes whose every wave owns all NT co tiles: packed last tile when the real channels allow
-#define CONV_FAST_CASE_F32_PK(KH_, KW_, NCBI_, W_, TH_, NT_, NCO_, NWV_)                                  \
-  if (CONV_FAST_MATCH(KH_, KW_, NCBI_, W_, TH_, NT_, NCO_)) {                                           \
-    if (pk_ok(a, NT_)) {                                                                                \
-      CONV_FAST_LAUNCH_PK(KH_, KW_, NCBI_, W_, TH_, NT_, NCO_, NWV_, 1, 1)                              \
-    }                                                                                                   \
-    CONV_FAST_LAUNCH(KH_, KW_, NCBI_, W_, TH_, NT_, NCO_, NWV_, 1)                                      \
-  }
-
-#define WGRAD_FAST_CASE(KH_, KW_, NCBI_, NCBO_, W_, R_, NW_, NB_)                                         \
-  if (a->KH == KH_ && a->KW == KW_ && a->Cinp == NCBI_ * 8 && a->Coutp == NCBO_ * 8 && a->W == W_ &&     \
-      a->H % R_ == 0 && a->pps % (R_ * W_) == 0) {                                                        \
-    dim3 grid(a->S, a->ngroups);                                                                         \
-    if ((g_wgrad_nb ? g_wgrad_nb : NB_) == 1)                                                            \
-      hipLaunchKernelGGL((wgrad_fast_kernel<KH_, KW_, NCBI_, NCBO_, W_, R_, NW_, 1>), grid, dim3(NW_ * 64), 0, stream, *a); \
-    else                                                                                                 \
-      hipLaunchKernelGGL((wgrad_fast_kernel<KH_, KW_, NCBI_, NCBO_, W_, R_, NW_, 2>), grid, dim3(NW_ * 64), 0, stream, *a); \
-    return (int)hipGetLastError();                                                                       \
-  }
-
-#define WGRAD_F32_LAUNCH(KH_, KW_, NCBI_, NCBO_, W_, R_, NW_, NB_, PK_)                                   \
-  hipLaunchKernelGGL((wgrad_fast_f32_kernel<KH_, KW_, NCBI_, NCBO_, W_, R_, NW_, NB_, PK_>), grid,           \
-                     dim3(NW_ * 64), 0, stream, *a)
-#define WGRAD_FAST_CASE_F32(KH_, KW_, NCBI_, NCBO_, W_, R_, NW_, NB_)                                     \
-  if (a->KH == KH_ && a->KW == KW_ && a->Cinp == NCBI_ * 8 && a->Coutp == NCBO_ * 8 && a->W == W_ &&     \
-      a->H % R_ == 0 && a->pps % (R_ * W_) == 0) {                                                        \
-    const int nz_ = wgrad_nz(a);                                                                         \
-    if (nz_ > 1) {                                                                                       \
-      dim3 gz(a->S, a->ngroups, nz_);                                                                    \
-      const bool pkz = wgrad_pk_ok(a, (NCBO_ * 8 + 15) / 16);                                            \
-      if (nz_ == 2) {                                                                                    \
-        /* the shape's band buffers (2 for the 16-wide stage: its 2 x S x G workgroups fit one per CU) */  \
-        if (pkz) hipLaunchKernelGGL((wgrad_fast_f32_kernel<KH_, KW_, NCBI_, NCBO_, W_, R_, NW_, NB_, 1, 2>), gz, \
-                                    dim3(NW_ * 64), 0, stream, *a);                                      \
-        else hipLaunchKernelGGL((wgrad_fast_f32_kernel<KH_, KW_, NCBI_, NCBO_, W_, R_, NW_, NB_, 0, 2>), gz,     \
-                                dim3(NW_ * 64), 0, stream, *a);                                          \
-      } else if (nz_ == 8) {                                                                             \
-        /* tiny launches (< 32 split x group blocks): 8 slices of 4-wave workgroups */                   \
-        if (pkz) hipLaunchKernelGGL((wgrad_fast_f32_kernel<KH_, KW_, NCBI_, NCBO_, W_, R_, 4, 1, 1, 8>), gz, \
-                                    dim3(256), 0, stream, *a);                                           \
-        else hipLaunchKernelGGL((wgrad_fast_f32_kernel<KH_, KW_, NCBI_, NCBO_, W_, R_, 4, 1, 0, 8>), gz,     \
-                                dim3(256), 0, stream, *a);                                               \
-      } else {                                                                                           \
-        if (pkz) hipLaunchKernelGGL((wgrad_fast_f32_kernel<KH_, KW_, NCBI_, NCBO_, W_, R_, NW_, 1, 1, 4>), gz, \
-                                    dim3(NW_ * 64), 0, stream, *a);                                      \
-        else hipLaunchKernelGGL((wgrad_fast_f32_kernel<KH_, KW_, NCBI_, NCBO_, W_, R_, NW_, 1, 0, 4>), gz,     \
-                                dim3(NW_ * 64), 0, stream, *a);                                          \
-      }                                                                                                  \
-      return (int)hipGetLastError();                                                                     \
-    }                                                                                                    \
-    dim3 grid(a->S, a->ngroups);                                                                         \
-    const bool pk = wgrad_pk_ok(a, (NCBO_ * 8 + 15) / 16);                                               \
-    if ((g_wgrad_nb ? g_wgrad_nb : NB_) == 1) {                                                          \
-      if (pk) WGRAD_F32_LAUNCH(KH_, KW_, NCBI_, NCBO_, W_, R_, NW_, 1, 1);                               \
-      else WGRAD_F32_LAUNCH(KH_, KW_, NCBI_, NCBO_, W_, R_, NW_, 1, 0);                                  \
-    } else {                                                                                             \
-      if (pk) WGRAD_F32_LAUNCH(KH_, KW_, NCBI_, NCBO_, W_, R_, NW_, 2, 1);                               \
-      else WGRAD_F32_LAUNCH(KH_, KW_, NCBI_, NCBO_, W_, R_, NW_, 2, 0);                                  \
-    }                                                                                                    \
-    return (int)hipGetLastError();                                                                       \
-  }
-
-// wide layers: NZ column slices per (split, group), single band buffer
-#define WGRAD_FAST_CASE_F32Z(KH_, KW_, NCBI_, NCBO_, W_, R_, NW_, NZ_)                                    \
-  if (a->KH == KH_ && a->KW == KW_ && a->Cinp == NCBI_ * 8 && a->Coutp == NCBO_ * 8 && a->W == W_ &&     \
-      a->H % R_ == 0 && a->pps % (R_ * W_) == 0) {                                                        \
-    dim3 grid(a->S, a->ngroups, NZ_);                                                                    \
-    if (wgrad_pk_ok(a, (NCBO_ * 8 + 15) / 16))                                                           \
-      hipLaunchKernelGGL((wgrad_fast_f32_kernel<KH_, KW_, NCBI_, NCBO_, W_, R_, NW_, 1, 1, NZ_>), grid,       \
-                         dim3(NW_ * 64), 0, stream, *a);                                                 \
-    else                                                                                                 \
-      hipLaunchKernelGGL((wgrad_fast_f32_kernel<KH_, KW_, NCBI_, NCBO_, W_, R_, NW_, 1, 0, NZ_>), grid,       \
-                         dim3(NW_ * 64), 0, stream, *a);                                                 \
-    return (int)hipGetLastError();                                                                       \
-  }
-
-// packed last co tile of the fp32 wgrad
-static bool wgrad_pk_ok(const WgradArgs* a, int mt) {
-  const int last = a->cout_real - 16 * (mt - 1);
-  return a->cout_real > 0 && last >= 1 && last <= 4;
+template <int KH, int KW, int NCBI, int NCBO, int W, int R, int NW, int NB, int PK = 0, int NZ = 1>
+static WgradKernel wgrad_kernel_f32() {
+  return {KH, KW, NCBI, NCBO, W, R, NW, NB, PK, NZ, 1,
+          reinterpret_cast<const void*>(&wgrad_fast_f32_kernel<KH, KW, NCBI, NCBO, W, R, NW, NB, PK, NZ>)};
+}
+template <int KH, int KW, int NCBI, int NCBO, int W, int R, int NW, int NB>
+static WgradKernel wgrad_kernel_bf16() {
+  return {KH, KW, NCBI, NCBO, W, R, NW, NB, 0, 1, 0,
+          reinterpret_cast<const void*>(&wgrad_fast_kernel<KH, KW, NCBI, NCBO, W, R, NW, NB>)};
 }
 
+// One geometry (KH, KW, Cinp / 8, Coutp / 8, W, prec) with H % R == 0 and whole bands of R rows per split
+// (pps % (R * W) == 0). select_wgrad works out (NW, NB, PK, NZ) from the row and the switches and runs the
+// kernel of `k` that has them.
+struct WgradRow {
+  int KH, KW, NCBI, NCBO, W, R, NW, PREC;
+  int NB;   // band buffers unless forced (gt_wgrad_set_nb)
+  int NZ;   // column slices per (split, group); 0: automatic (wgrad_nz: NZ 2 keeps NB, NZ 4 has one band
+            // buffer, NZ 8 one buffer and 4-wave workgroups)
+  std::vector<WgradKernel> k;
+};
+
+// fp32, automatic column slices
+template <int KH, int KW, int NCBI, int NCBO, int W, int R, int NW, int NB>
+static WgradRow wgrad_f32() {
+  return {KH, KW, NCBI, NCBO, W, R, NW, 1, NB, 0,
+          {wgrad_kernel_f32<KH, KW, NCBI, NCBO, W, R, NW, 1, 0>(), wgrad_kernel_f32<KH, KW, NCBI, NCBO, W, R, NW, 1, 1>(),
+           wgrad_kernel_f32<KH, KW, NCBI, NCBO, W, R, NW, 2, 0>(), wgrad_kernel_f32<KH, KW, NCBI, NCBO, W, R, NW, 2, 1>(),
+           wgrad_kernel_f32<KH, KW, NCBI, NCBO, W, R, NW, NB, 0, 2>(), wgrad_kernel_f32<KH, KW, NCBI, NCBO, W, R, NW, NB, 1, 2>(),
+           wgrad_kernel_f32<KH, KW, NCBI, NCBO, W, R, NW, 1, 0, 4>(), wgrad_kernel_f32<KH, KW, NCBI, NCBO, W, R, NW, 1, 1, 4>(),
+           wgrad_kernel_f32<KH, KW, NCBI, NCBO, W, R, 4, 1, 0, 8>(), wgrad_kernel_f32<KH, KW, NCBI, NCBO, W, R, 4, 1, 1, 8>()}};
+}
+// fp32 wide layers: NZ column slices per (split, group), single band buffer
+template <int KH, int KW, int NCBI, int NCBO, int W, int R, int NW, int NZ>
+static WgradRow wgrad_f32z() {
+  return {KH, KW, NCBI, NCBO, W, R, NW, 1, 1, NZ,
+          {wgrad_kernel_f32<KH, KW, NCBI, NCBO, W, R, NW, 1, 0, NZ>(), wgrad_kernel_f32<KH, KW, NCBI, NCBO, W, R, NW, 1, 1, NZ>()}};
+}
+template <int KH, int KW, int NCBI, int NCBO, int W, int R, int NW, int NB>
+static WgradRow wgrad_bf16() {
+  return {KH, KW, NCBI, NCBO, W, R, NW, 0, NB, 1,
+          {wgrad_kernel_bf16<KH, KW, NCBI, NCBO, W, R, NW, 1>(), wgrad_kernel_bf16<KH, KW, NCBI, NCBO, W, R, NW, 2>()}};
+}
+
+// rows of user-chosen architectures (cnn_conv_fast_ext.hip), walked after the search-space rows
+const std::vector<ConvRow>& conv_rows_ext();
+const std::vector<WgradRow>& wgrad_rows_ext();

@@ -563,8 +563,7 @@ class HipPopJob(FoldJob):
         # separate pool kernel otherwise (and with BatchNorm, which normalises
         # after the conv)
         L_ = self.L
-        fast_on = L_.gt_conv_set_fast(1)
-        L_.gt_conv_set_fast(fast_on)
+        fast_on = K.fast_path_on(L_)
         fuse_env = POOL_FUSE
         self.pool_fused = []
         for st in self.stages:

@@ -131,6 +131,19 @@ class WgradArgs(C.Structure):
                 ("cout_real", I)]
 
 
+class ConvSel(C.Structure):
+    """What gt_conv_fast would launch (gt_conv_fast_select): the conv_fast_kernel template parameters, its LDS
+    bytes for forward / other launches, and this launch's grid, block and LDS bytes."""
+    _fields_ = [(n, I) for n in ("KH", "KW", "NCBI", "W", "TH", "NT", "NCO", "NWV", "PREC", "PK", "RE", "CTX", "SCH",
+                                 "lds_fwd", "lds_bwd", "gx", "gy", "gz", "block", "lds")]
+
+
+class WgradSel(C.Structure):
+    """What gt_wgrad_fast would launch (gt_wgrad_fast_select): PREC 0 wgrad_fast_kernel, 1 wgrad_fast_f32_kernel."""
+    _fields_ = [(n, I) for n in ("KH", "KW", "NCBI", "NCBO", "W", "R", "NW", "NB", "PK", "NZ", "PREC",
+                                 "gx", "gy", "gz", "block", "lds")]
+
+
 class DenseFwdArgs(C.Structure):
     _fields_ = [("x", P), ("wt", P), ("bias", P), ("out", P), ("w2", P), ("plog", P), ("st", P), ("fold_ids", P),
                 ("seeds", P), ("G", I), ("B", I), ("Fp", I), ("Up", I), ("drop_p", C.c_float), ("train", I),
@@ -273,6 +286,14 @@ def lib():
         L.gt_conv_fast_probe.restype = I
         L.gt_conv_fast_probe_any.argtypes = [C.POINTER(ConvArgs)]
         L.gt_conv_fast_probe_any.restype = I
+        L.gt_conv_fast_select.argtypes = [C.POINTER(ConvArgs), C.POINTER(ConvSel)]
+        L.gt_conv_fast_select.restype = I
+        L.gt_wgrad_fast_select.argtypes = [C.POINTER(WgradArgs), C.POINTER(WgradSel)]
+        L.gt_wgrad_fast_select.restype = I
+        L.gt_sizeof_conv_sel.restype = C.c_size_t
+        assert L.gt_sizeof_conv_sel() == C.sizeof(ConvSel), "ConvSel ABI mismatch"
+        L.gt_sizeof_wgrad_sel.restype = C.c_size_t
+        assert L.gt_sizeof_wgrad_sel() == C.sizeof(WgradSel), "WgradSel ABI mismatch"
         L.gt_wgrad_reduce.argtypes = [C.POINTER(WgradArgs), P]
         L.gt_wgrad_reduce.restype = I
         L.gt_conv_frag_order.argtypes = [I, I, I, I, I, C.POINTER(C.c_int), I]
@@ -289,14 +310,12 @@ def lib():
         assert L.gt_sizeof_wino_wseg() == C.sizeof(WinoWSeg), "WinoWSeg ABI mismatch"
         L.gt_conv_set_fast.argtypes = [I]
         L.gt_conv_set_fast.restype = I
-        L.gt_conv_set_nwv.argtypes = [I]
-        L.gt_conv_set_s2in_ct1.restype = I
         L.gt_dense_fwd_splits.argtypes = [I]
         L.gt_dense_fwd_splits.restype = I
         L.gt_conv_set_smallq.argtypes = [I]
         L.gt_conv_set_smallq.restype = I
         L.gt_conv_set_s2in_ct1.argtypes = [I]
-        L.gt_conv_set_nwv.restype = I
+        L.gt_conv_set_s2in_ct1.restype = I
         L.gt_conv_set_imgs.argtypes = [I]
         L.gt_conv_set_imgs.restype = I
         L.gt_glorot_init.argtypes = [C.POINTER(InitArgs), I, P]
@@ -501,6 +520,13 @@ def padded_hw(h, w, nstages, batch_norm=False):
 FAST_PADS = (24, 32, 56, 64, 104, 128, 256)
 
 
+def fast_path_on(L):
+    """The fast-path switch (gt_conv_set_fast), read by setting it and putting the old value back."""
+    on = L.gt_conv_set_fast(1)
+    L.gt_conv_set_fast(on)
+    return bool(on)
+
+
 def _probe_conv(L, KH, KW, cinp, coutp, H, W, prec, ngroups, B, cout_real, fwd):
     a = ConvArgs()
     a.KH, a.KW, a.Cinp, a.Coutp, a.H, a.W = KH, KW, cinp, coutp, H, W
@@ -515,9 +541,7 @@ def layer_fast(KH, KW, cinp, coutp, H, W, prec, ngroups, B, cin_real, cout_real,
     """(forward, data gradient, weight gradient) of one layer geometry run on shape-specialised kernels
     (gt_conv_fast / gt_wgrad_fast) -- each probed without launching anything (no GPU needed)."""
     L = lib()
-    on = L.gt_conv_set_fast(1)               # the fast path switched off (generic-kernel comparisons): none
-    L.gt_conv_set_fast(on)
-    if not on:
+    if not fast_path_on(L):                  # the fast path switched off (generic-kernel comparisons): none
         return False, False, False
     fwd = _probe_conv(L, KH, KW, cinp, coutp, H, W, prec, ngroups, B, cout_real, True)
     dgr = True if first else _probe_conv(L, KH, KW, coutp, cinp, H, W, prec, ngroups, B, cin_real, False)
@@ -574,8 +598,7 @@ def wgrad_band(KH, KW, cinp, coutp, H, W, prec=0):
     """``(pixels per band, preferred splits)`` of the shape-specialised wgrad
     kernel, or ``(0, 0)`` for the generic one."""
     L = lib()
-    if not L.gt_conv_set_fast(1):       # probe + restore the fast-path switch
-        L.gt_conv_set_fast(0)
+    if not fast_path_on(L):
         return 0, 0
     band = int(L.gt_wgrad_fast_band(KH, KW, cinp, coutp, H, W, prec))
     splits = int(L.gt_wgrad_fast_splits(KH, KW, cinp, coutp, H, W, prec)) if band else 0
