@@ -625,10 +625,14 @@ __global__ void __launch_bounds__(256) partition_kernel(Geo geo, int depth, cons
     ends[j] = nd.start + nd.count;
   }
   __syncthreads();
-  auto node_of = [&](int p) {                  // node whose segment holds position p, or -1
+  // node whose segment holds position p; negative when p lies in no segment (rows of an earlier leaf):
+  // -1 - lo names the dead gap in front of node lo, so that two positions with the SAME negative value have
+  // nothing but dead positions between them (equal -1s did not say that: a block whose first and last
+  // positions were dead returned early and left the live nodes between them unpartitioned)
+  auto node_of = [&](int p) {
     int lo = 0, hi = L;
     while (lo < hi) { const int mid = (lo + hi) >> 1; if (ends[mid] > p) hi = mid; else lo = mid + 1; }
-    return (lo < L && cur[(size_t)k * geo.Lmax + lo].start <= p) ? lo : -1;
+    return (lo < L && cur[(size_t)k * geo.Lmax + lo].start <= p) ? lo : -1 - lo;
   };
   if (tid == 0) {
     jfl[0] = node_of(p0);
@@ -939,6 +943,36 @@ std::mutex mu;
 void invalidate_derived() { g_binsT_key = 0; }
 }  // namespace gbdt_cache
 
+// ---- stage trace (tests/test_gbdt_stages.py): with a sink, the host synchronises after the stage that
+// produces a buffer, copies it to a host vector and hands it to the sink. Every site is one
+// `if (sink && round < trace_rounds && (trace_mask & TAG))`: with a null sink (gbdt_cv_hip) no launch, copy or
+// synchronisation is added. Per-tree and per-round blocks carry depth -1 (the margins before the tree's
+// gradients: -2).
+extern "C" typedef void (*gbdt_trace_fn)(void* user, int round, int cls, int depth, int tag, const void* host_data,
+                                         long long bytes);
+enum : unsigned {
+  GT_GH = 1u << 0,       // float2 [nfold][n]
+  GT_MX = 1u << 1,       // unsigned [nfold][2]: bit patterns of max |g|, max |h|
+  GT_KEYS = 1u << 2,     // u64 [nfold]: the tree's row-subsample keys
+  GT_ORDER = 1u << 3,    // int [nfold][D + 1][F]: 1 + scan position, 0 = not sampled
+  GT_ROOT = 1u << 4,     // int [nfold] root row counts, then int [nfold][n] the level-0 row list
+  GT_TREE = 1u << 5,     // int2 [nfold][2^(D+1) - 1]
+  GT_LEAF = 1u << 6,     // float [nfold][2^(D+1) - 1]
+  GT_MARGIN = 1u << 7,   // float [nfold][n][K]; depth -2 before the tree's gradients, -1 after predict
+  GT_LNODES = 1u << 8,   // LNode [nfold][Lmax]: the level's nodes (after root_totals / plan_next)
+  GT_CHUNKS = 1u << 9,   // Chunk [nfold][maxch]
+  GT_REDS = 1u << 10,    // Red [nfold][maxch]
+  GT_COUNTS = 1u << 11,  // int [nfold][2]: chunks, reductions
+  GT_HIST = 1u << 12,    // i64 [nfold][Lh][F][256][2] (heavy)
+  GT_CAND = 1u << 13,    // SplitOut [nfold][Lh][F] (heavy)
+  GT_BEST = 1u << 14,    // NodeBest [nfold][Lh]
+  GT_SPLITV = 1u << 15,  // int2 [nfold][Lmax]
+  GT_ROWS = 1u << 16,    // int [nfold][n]: the partition's output list
+  GT_NXT = 1u << 17,     // LNode [nfold][Lmax]: the next level's nodes after plan_next
+  GT_MET = 1u << 18,     // double [n_metrics][nfold][mblocks][4] partial sums
+  GT_AUC = 1u << 19,     // double [nfold][4]: train rank sum, train positives, test rank sum, test positives
+};
+
 extern "C" {
 
 // Same contract as gbdt_cv (csrc/gbdt/engine.cpp) for every objective
@@ -951,10 +985,11 @@ extern "C" {
 // ROW-major [n][Fs] uint8 (Fs >= F, Fs % 4 == 0). cache_key != 0 keeps the
 // device copy of the bins across calls for the same key (one dataset, many
 // candidates).
-int gbdt_cv_hip(const uint8_t* bins_h, int Fs, const int* nbins_h, int n, int F, const float* y_h,
-                const int* fold_h, int nfold, const double* P, int objective, int num_class, const int* metrics,
-                int n_metrics, int num_boost_round, int early_stopping_rounds, unsigned long long seed,
-                long long cache_key, double* out_hist) {
+static int gbdt_cv_body(const uint8_t* bins_h, int Fs, const int* nbins_h, int n, int F, const float* y_h,
+                        const int* fold_h, int nfold, const double* P, int objective, int num_class,
+                        const int* metrics, int n_metrics, int num_boost_round, int early_stopping_rounds,
+                        unsigned long long seed, long long cache_key, double* out_hist, int trace_rounds,
+                        unsigned trace_mask, gbdt_trace_fn sink, void* user) {
   if (objective < 0 || objective > 5 || n_metrics < 1 || Fs % 4 || Fs < F || n <= 0 || nfold <= 0 || F <= 0)
     return -1;
   bool want_auc = false;
@@ -1043,6 +1078,16 @@ int gbdt_cv_hip(const uint8_t* bins_h, int Fs, const int* nbins_h, int n, int F,
   static const bool timing = std::getenv("GENTUN_GBDT_TIMING") != nullptr;
   static const int progress = std::getenv("GENTUN_GBDT_PROGRESS") ? std::atoi(std::getenv("GENTUN_GBDT_PROGRESS")) : 0;
   const auto t_start = std::chrono::steady_clock::now();
+  // trace: wait for the stage, copy its buffer(s) to the host, hand them to the sink as one block
+  auto emit = [&](int round, int cls, int depth, unsigned tag, const void* dev, size_t bytes,
+                  const void* dev2 = nullptr, size_t bytes2 = 0) -> hipError_t {
+    std::vector<char> h(bytes + bytes2);
+    hipError_t e = hipStreamSynchronize(0);
+    if (e == hipSuccess) e = hipMemcpy(h.data(), dev, bytes, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && bytes2) e = hipMemcpy(h.data() + bytes, dev2, bytes2, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) sink(user, round, cls, depth, (int)tag, h.data(), (long long)h.size());
+    return e;
+  };
 
   {
     const size_t nbytes = (size_t)n * Fs;
@@ -1150,16 +1195,28 @@ int gbdt_cv_hip(const uint8_t* bins_h, int Fs, const int* nbins_h, int n, int F,
     HC(hipMemcpyAsync(d_order, h_order, sizeof(int) * K * order_elems, hipMemcpyHostToDevice, 0));
     // ---- device: one tree per class for every fold, levels decided on the device
     for (int c = 0; c < K; ++c) {
+      if (sink && round < trace_rounds && (trace_mask & GT_KEYS))
+        HC(emit(round, c, -1, GT_KEYS, d_keys + (size_t)c * nfold, sizeof(u64) * nfold));
+      if (sink && round < trace_rounds && (trace_mask & GT_ORDER))
+        HC(emit(round, c, -1, GT_ORDER, d_order + (size_t)c * order_elems, sizeof(int) * order_elems));
+      if (sink && round < trace_rounds && (trace_mask & GT_MARGIN))
+        HC(emit(round, c, -2, GT_MARGIN, d_margin, sizeof(float) * (size_t)nfold * n * K));
       hipLaunchKernelGGL(grad_kernel, dim3(blocks, nfold), dim3(256), 0, 0, d_margin, d_y, d_gh, n, K, c, obj,
                          (float)P[10]);
       HC(hipMemsetAsync(d_mx, 0, sizeof(unsigned int) * 2 * nfold, 0));
       hipLaunchKernelGGL(gh_max_kernel, dim3(std::min(blocks, 256), nfold), dim3(256), 0, 0, d_gh, n, d_mx);
+      if (sink && round < trace_rounds && (trace_mask & GT_GH))
+        HC(emit(round, c, -1, GT_GH, d_gh, sizeof(float2) * (size_t)nfold * n));
+      if (sink && round < trace_rounds && (trace_mask & GT_MX))
+        HC(emit(round, c, -1, GT_MX, d_mx, sizeof(unsigned int) * 2 * nfold));
       HC(hipMemsetAsync(d_nroot, 0, sizeof(int) * nfold, 0));
       hipLaunchKernelGGL(root_rows_kernel, dim3(std::max(1, std::min(1024, (n + 256 * RR_PER - 1) / (256 * RR_PER))), nfold),
                          dim3(256), 0, 0, d_fold, n, d_keys + (size_t)c * nfold,
                          P[5], d_rows[0], d_nroot);
       hipLaunchKernelGGL(level0_kernel, dim3(nfold), dim3(64), 0, 0, geo, d_nroot, d_lvl[0], d_chunks, d_reds,
                          d_counts);
+      if (sink && round < trace_rounds && (trace_mask & GT_ROOT))
+        HC(emit(round, c, -1, GT_ROOT, d_nroot, sizeof(int) * nfold, d_rows[0], sizeof(int) * (size_t)nfold * n));
       const int* order_c = d_order + (size_t)c * order_elems;
       for (int d = 0; d <= D; ++d) {
         const int L = 1 << d;
@@ -1183,24 +1240,50 @@ int gbdt_cv_hip(const uint8_t* bins_h, int Fs, const int* nbins_h, int n, int F,
           else if (d + 1 < D)
             hipLaunchKernelGGL(subtract_kernel, dim3(L, ylen, nfold), dim3(256), 0, 0, geo, cur, d_hist[(d - 1) & 1],
                                hcur);
+          if (sink && round < trace_rounds && (trace_mask & GT_HIST))
+            HC(emit(round, c, d, GT_HIST, hcur, sizeof(i64) * (size_t)nfold * geo.Lh * per_node));
         }
+        if (sink && round < trace_rounds && (trace_mask & GT_LNODES))
+          HC(emit(round, c, d, GT_LNODES, cur, sizeof(LNode) * (size_t)nfold * geo.Lmax));
+        if (sink && round < trace_rounds && (trace_mask & GT_CHUNKS))
+          HC(emit(round, c, d, GT_CHUNKS, d_chunks, sizeof(Chunk) * (size_t)nfold * geo.maxch));
+        if (sink && round < trace_rounds && (trace_mask & GT_REDS))
+          HC(emit(round, c, d, GT_REDS, d_reds, sizeof(Red) * (size_t)nfold * geo.maxch));
+        if (sink && round < trace_rounds && (trace_mask & GT_COUNTS))
+          HC(emit(round, c, d, GT_COUNTS, d_counts, sizeof(int) * 2 * nfold));
         if (d < D) {
           hipLaunchKernelGGL(split_kernel, dim3(F, L, nfold), dim3(64), 0, 0, geo, d, hcur,
                              (d > 0 && d + 1 == D) ? d_hist[(d - 1) & 1] : nullptr, d_nb, order_c, cur, d_mx, d_cand,
                              dp);
+          if (sink && round < trace_rounds && (trace_mask & GT_CAND))
+            HC(emit(round, c, d, GT_CAND, d_cand, sizeof(SplitOut) * (size_t)nfold * geo.Lh * F));
           hipLaunchKernelGGL(best_kernel, dim3(L, nfold), dim3(256), 0, 0, geo, d_cand, d_best);
+          if (sink && round < trace_rounds && (trace_mask & GT_BEST))
+            HC(emit(round, c, d, GT_BEST, d_best, sizeof(NodeBest) * (size_t)nfold * geo.Lh));
         }
         hipLaunchKernelGGL(plan_split_kernel, dim3(nfold), dim3(256), 0, 0, geo, d, cur, d_best, d_mx, d_tree, d_leaf,
                            d_split, d_cur, nxt, dp);
+        if (sink && round < trace_rounds && (trace_mask & GT_SPLITV))
+          HC(emit(round, c, d, GT_SPLITV, d_split, sizeof(int2) * (size_t)nfold * geo.Lmax));
         if (d < D) {
           hipLaunchKernelGGL(partition_kernel, dim3(pblocks, nfold), dim3(256), 0, 0, geo, d, g_binsT, d_nroot, cur,
                              d_split, d_rows[d & 1], d_rows[(d + 1) & 1], d_cur);
+          if (sink && round < trace_rounds && (trace_mask & GT_ROWS))
+            HC(emit(round, c, d, GT_ROWS, d_rows[(d + 1) & 1], sizeof(int) * (size_t)nfold * n));
           hipLaunchKernelGGL(plan_next_kernel, dim3(nfold), dim3(256), 0, 0, geo, d, cur, d_split, d_cur, nxt,
                              d_chunks, d_reds, d_counts);
+          if (sink && round < trace_rounds && (trace_mask & GT_NXT))
+            HC(emit(round, c, d, GT_NXT, nxt, sizeof(LNode) * (size_t)nfold * geo.Lmax));
         }
       }
+      if (sink && round < trace_rounds && (trace_mask & GT_TREE))
+        HC(emit(round, c, -1, GT_TREE, d_tree, sizeof(int2) * (size_t)nfold * tsz));
+      if (sink && round < trace_rounds && (trace_mask & GT_LEAF))
+        HC(emit(round, c, -1, GT_LEAF, d_leaf, sizeof(float) * (size_t)nfold * tsz));
       hipLaunchKernelGGL(predict_kernel, dim3(std::min(blocks, 512), (nfold + pk - 1) / pk), dim3(256), pred_lds, 0,
                          geo, d_bins, d_tree, d_leaf, d_margin, c, pk, pr_rows);
+      if (sink && round < trace_rounds && (trace_mask & GT_MARGIN))
+        HC(emit(round, c, -1, GT_MARGIN, d_margin, sizeof(float) * (size_t)nfold * n * K));
     }
     for (int mi = 0; mi < n_metrics; ++mi)
       if (metrics[mi] != 4)
@@ -1217,6 +1300,10 @@ int gbdt_cv_hip(const uint8_t* bins_h, int Fs, const int* nbins_h, int n, int F,
     // the round's blocking copies: early stopping needs the test metric
     HC(hipMemcpy(h_met, d_met, sizeof(double) * met_elems, hipMemcpyDeviceToHost));
     if (want_auc) HC(hipMemcpy(h_aacc.data(), d_aacc, sizeof(double) * 4 * nfold, hipMemcpyDeviceToHost));
+    if (sink && round < trace_rounds && (trace_mask & GT_MET))
+      sink(user, round, -1, -1, (int)GT_MET, h_met, (long long)(sizeof(double) * met_elems));
+    if (sink && round < trace_rounds && (trace_mask & GT_AUC) && want_auc)
+      sink(user, round, -1, -1, (int)GT_AUC, h_aacc.data(), (long long)(sizeof(double) * 4 * nfold));
     double tem_last = 0;
     for (int mi = 0; mi < n_metrics; ++mi) {
       std::vector<double> trv(nfold), tev(nfold);
@@ -1271,6 +1358,35 @@ done:
   if (h_up) (void)hipHostFree(h_up);
   if (h_met) (void)hipHostFree(h_met);
   return rc;
+}
+
+int gbdt_cv_hip(const uint8_t* bins_h, int Fs, const int* nbins_h, int n, int F, const float* y_h,
+                const int* fold_h, int nfold, const double* P, int objective, int num_class, const int* metrics,
+                int n_metrics, int num_boost_round, int early_stopping_rounds, unsigned long long seed,
+                long long cache_key, double* out_hist) {
+  return gbdt_cv_body(bins_h, Fs, nbins_h, n, F, y_h, fold_h, nfold, P, objective, num_class, metrics, n_metrics,
+                      num_boost_round, early_stopping_rounds, seed, cache_key, out_hist, 0, 0u, nullptr, nullptr);
+}
+
+// gbdt_cv_hip with the stage trace: the first trace_rounds rounds hand the buffers selected by trace_mask
+// (GT_* bits) to sink. Same computation and return value.
+int gbdt_cv_hip_trace(const uint8_t* bins_h, int Fs, const int* nbins_h, int n, int F, const float* y_h,
+                      const int* fold_h, int nfold, const double* P, int objective, int num_class,
+                      const int* metrics, int n_metrics, int num_boost_round, int early_stopping_rounds,
+                      unsigned long long seed, long long cache_key, double* out_hist, int trace_rounds,
+                      unsigned trace_mask, gbdt_trace_fn sink, void* user) {
+  return gbdt_cv_body(bins_h, Fs, nbins_h, n, F, y_h, fold_h, nfold, P, objective, num_class, metrics, n_metrics,
+                      num_boost_round, early_stopping_rounds, seed, cache_key, out_hist, trace_rounds, trace_mask,
+                      sink, user);
+}
+
+// struct sizes and constants the trace's reader needs: sizeof LNode, Chunk, Red, SplitOut, NodeBest; GB_R,
+// HB_FC, HB_FG, GB_MAXD (9 ints)
+int gbdt_trace_layout(int* out) {
+  const int v[9] = {(int)sizeof(LNode), (int)sizeof(Chunk), (int)sizeof(Red), (int)sizeof(SplitOut),
+                    (int)sizeof(NodeBest), GB_R, HB_FC, HB_FG, GB_MAXD};
+  for (int i = 0; i < 9; ++i) out[i] = v[i];
+  return 9;
 }
 
 }  // extern "C"

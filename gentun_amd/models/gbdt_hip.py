@@ -148,3 +148,85 @@ def cv(x, y, fold_of, nfold, parr, obj, num_class, marr, nrounds, esr, seed, his
         if kept != -7:                       # -7: another dataset evicted the device bins
             return kept
     return kept
+
+
+# ---- stage trace (csrc/hip/gbdt_hist.hip gbdt_cv_hip_trace; tests/test_gbdt_stages.py) --------------------
+TRACE_TAGS = ("GH", "MX", "KEYS", "ORDER", "ROOT", "TREE", "LEAF", "MARGIN", "LNODES", "CHUNKS", "REDS", "COUNTS",
+              "HIST", "CAND", "BEST", "SPLITV", "ROWS", "NXT", "MET", "AUC")     # bit i of the mask = TRACE_TAGS[i]
+TRACE_HEAVY = ("HIST", "CAND")
+LNODE = np.dtype([("start", "<i4"), ("count", "<i4"), ("G", "<i8"), ("H", "<i8"), ("exists", "<i4"),
+                  ("built", "<i4"), ("parent", "<i4"), ("pad", "<i4")])
+CHUNK = np.dtype([("node", "<i4"), ("start", "<i4"), ("count", "<i4"), ("slot", "<i4")])
+RED = np.dtype([("node", "<i4"), ("first", "<i4"), ("nslots", "<i4"), ("pad", "<i4")])
+SPLITOUT = np.dtype([("gain", "<f8"), ("GL", "<i8"), ("HL", "<i8"), ("bin", "<i4"), ("order", "<i4")])
+NODEBEST = np.dtype([("gain", "<f8"), ("GL", "<i8"), ("HL", "<i8"), ("feature", "<i4"), ("bin", "<i4")])
+INT2 = np.dtype([("x", "<i4"), ("y", "<i4")])
+TRACE_DTYPES = {"GH": np.dtype("<f4"), "MX": np.dtype("<u4"), "KEYS": np.dtype("<u8"), "ORDER": np.dtype("<i4"),
+                "ROOT": np.dtype("<i4"), "TREE": INT2, "LEAF": np.dtype("<f4"), "MARGIN": np.dtype("<f4"),
+                "LNODES": LNODE, "CHUNKS": CHUNK, "REDS": RED, "COUNTS": np.dtype("<i4"), "HIST": np.dtype("<i8"),
+                "CAND": SPLITOUT, "BEST": NODEBEST, "SPLITV": INT2, "ROWS": np.dtype("<i4"), "NXT": LNODE,
+                "MET": np.dtype("<f8"), "AUC": np.dtype("<f8")}
+_SINK = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                         ctypes.c_void_p, ctypes.c_longlong)
+
+
+def trace_mask(tags):
+    m = 0
+    for t in tags:
+        m |= 1 << TRACE_TAGS.index(t)
+    return m
+
+
+def trace_layout():
+    """Struct sizes and constants of the engine: sizeof LNode, Chunk, Red, SplitOut, NodeBest; GB_R, HB_FC,
+    HB_FG, GB_MAXD."""
+    f = _lib.hip().gbdt_trace_layout
+    f.argtypes = [ctypes.c_void_p]
+    f.restype = ctypes.c_int
+    out = np.zeros(9, np.int32)
+    if f(out.ctypes.data) != 9:
+        raise RuntimeError("gbdt_trace_layout: unexpected length")
+    return dict(zip(("LNode", "Chunk", "Red", "SplitOut", "NodeBest", "GB_R", "HB_FC", "HB_FG", "GB_MAXD"),
+                    (int(v) for v in out)))
+
+
+def _tfn():
+    f = _lib.hip().gbdt_cv_hip_trace
+    if not getattr(f, "_typed", False):
+        c = ctypes
+        f.argtypes = list(_fn().argtypes) + [c.c_int, c.c_uint, _SINK, c.c_void_p]
+        f.restype = c.c_int
+        f._typed = True
+    return f
+
+
+def cv_trace(x, y, fold_of, nfold, parr, obj, num_class, marr, nrounds, esr, seed, hist, trace_rounds=1,
+             tags=None, x_key=None):
+    """:func:`cv` through ``gbdt_cv_hip_trace``: returns ``(kept, {(round, cls, depth, tag): ndarray})`` with
+    the engine's buffers after every stage of the first ``trace_rounds`` rounds (flat arrays of
+    ``TRACE_DTYPES[tag]``; per-tree and per-round blocks have depth -1, the margins before a tree -2).
+    ``tags`` defaults to every tag but the heavy ones (``TRACE_HEAVY``)."""
+    if not supported(obj, marr, nfold):
+        raise ValueError("objective / metrics not supported by the GPU engine")
+    tags = [t for t in TRACE_TAGS if t not in TRACE_HEAVY] if tags is None else list(tags)
+    blocks = {}
+
+    def sink(_user, rnd, cls, depth, tag, data, nbytes):
+        name = TRACE_TAGS[int(tag).bit_length() - 1]
+        blocks[(rnd, cls, depth, name)] = np.frombuffer(ctypes.string_at(data, nbytes), dtype=TRACE_DTYPES[name])
+
+    cb = _SINK(sink)
+    xk = x if x_key is None else x_key
+    fold_of = np.ascontiguousarray(fold_of.astype(np.int32))
+    y = np.ascontiguousarray(y.astype(np.float32))
+    marr = np.ascontiguousarray(marr.astype(np.int32))
+    for attempt in (0, 1):
+        blocks.clear()
+        nb, key, fs = quantize_device(x, force=attempt > 0, ident=xk)
+        kept = _tfn()(None, fs, nb.ctypes.data, x.shape[0], x.shape[1], y.ctypes.data, fold_of.ctypes.data,
+                      int(nfold), parr.ctypes.data, int(obj), int(num_class), marr.ctypes.data, len(marr),
+                      int(nrounds), int(esr), ctypes.c_ulonglong(seed & 0xFFFFFFFFFFFFFFFF), key, hist.ctypes.data,
+                      int(trace_rounds), trace_mask(tags), cb, None)
+        if kept != -7:
+            break
+    return kept, blocks
