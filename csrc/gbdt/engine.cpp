@@ -16,9 +16,8 @@
 //
 // Folds advance in lock-step (one boosting round of every fold, then the
 // early-stopping check), each fold on its own thread. Deterministic: all
-// sampling comes from a splitmix64 stream keyed by (seed, fold, round, node).
-// The HIP kernels in hist.hip implement G3/G4 on MI355X for large data; the
-// host engine owns the tree bookkeeping for both.
+// sampling comes from a splitmix64 stream keyed by (seed, fold, round, class).
+// What the MI355X engine (csrc/hip/gbdt_hist.hip) shares with this one: cv_protocol.h.
 
 #include <algorithm>
 #include <atomic>
@@ -30,57 +29,13 @@
 #include <thread>
 #include <vector>
 
+#include "cv_protocol.h"
+
 namespace {
 
+using namespace gbdt;
+
 constexpr int kMaxBin = 256;
-
-enum Objective { OBJ_SQUARED = 0, OBJ_LOGISTIC = 1, OBJ_BINARY_LOGISTIC = 2, OBJ_BINARY_LOGITRAW = 3,
-                 OBJ_MULTI_SOFTMAX = 4, OBJ_MULTI_SOFTPROB = 5 };
-enum Metric { M_RMSE = 0, M_MAE = 1, M_LOGLOSS = 2, M_ERROR = 3, M_AUC = 4, M_MERROR = 5, M_MLOGLOSS = 6 };
-
-struct Params {
-  double eta, min_child_weight, max_depth, gamma, max_delta_step, subsample, colsample_bytree,
-      colsample_bylevel, lambda, alpha, scale_pos_weight, base_score;
-};
-
-inline uint64_t splitmix(uint64_t x) {
-  x += 0x9E3779B97F4A7C15ull;
-  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-  return x ^ (x >> 31);
-}
-struct Rng {
-  uint64_t s;
-  explicit Rng(uint64_t seed) : s(seed) {}
-  uint64_t next() { s = splitmix(s); return s; }
-  double uniform() { return (next() >> 11) * (1.0 / 9007199254740992.0); }
-};
-
-inline double row_uniform(uint64_t key, uint64_t row) {
-  return (splitmix(key ^ splitmix(row)) >> 11) * (1.0 / 9007199254740992.0);
-}
-
-inline double threshold_l1(double g, double alpha) {
-  if (g > alpha) return g - alpha;
-  if (g < -alpha) return g + alpha;
-  return 0.0;
-}
-inline double calc_weight(const Params& p, double G, double H) {
-  if (H < p.min_child_weight || H <= 0.0) return 0.0;
-  double w = -threshold_l1(G, p.alpha) / (H + p.lambda);
-  if (p.max_delta_step != 0.0 && std::fabs(w) > p.max_delta_step) w = std::copysign(p.max_delta_step, w);
-  return w;
-}
-inline double calc_gain(const Params& p, double G, double H) {
-  if (H < p.min_child_weight || H <= 0.0) return 0.0;
-  if (p.max_delta_step == 0.0) {
-    double t = threshold_l1(G, p.alpha);
-    return t * t / (H + p.lambda);
-  }
-  double w = calc_weight(p, G, H);
-  double ret = -(2.0 * G * w + (H + p.lambda) * w * w);
-  return p.alpha == 0.0 ? ret : ret + p.alpha * std::fabs(w);
-}
 
 struct Quantized {
   int n = 0, F = 0;
@@ -178,25 +133,14 @@ struct SplitResult {
   double gain = 0.0; int feature = -1, bin = -1; double GL = 0, HL = 0;
 };
 
-// Build one tree on rows `rows` (indices into the dataset) with grad/hess `gh`.
+// Build one tree on rows `rows` (indices into the dataset) with grad/hess `gh`
+// and the tree's draws `draws` (cv_protocol.h draw_tree).
 Tree build_tree(const Quantized& q, const std::vector<GH>& gh, std::vector<int>& rows, const Params& p,
-                Rng& rng) {
+                const TreeDraws& draws) {
   const int F = q.F;
   const int max_depth = std::max(0, (int)p.max_depth);
   Tree tree;
-  // colsample_bytree
-  std::vector<int> feats(F);
-  std::iota(feats.begin(), feats.end(), 0);
-  if (p.colsample_bytree < 1.0) {
-    int k = std::max(1, (int)std::floor(p.colsample_bytree * F + 1e-9));
-    for (int i = 0; i < F; ++i) std::swap(feats[i], feats[i + (int)(rng.next() % (uint64_t)(F - i))]);
-    feats.resize(k);
-    std::sort(feats.begin(), feats.end());
-  }
-  // colsample_bylevel: one draw keys the level streams (level d shuffles with
-  // its own stream), so the tree stream's draw count does not depend on how
-  // deep the tree grows -- the GPU engine precomputes every level's features
-  const uint64_t level_key = p.colsample_bylevel < 1.0 ? rng.next() : 0ull;
+  const std::vector<int>& feats = draws.feats;
   struct Work { int node; int begin, end; std::vector<GH> hist; double G, H; };
   auto build_hist = [&](int b, int e, std::vector<GH>& hist) {
     hist.assign((size_t)F * kMaxBin, GH{0.0, 0.0});
@@ -220,15 +164,7 @@ Tree build_tree(const Quantized& q, const std::vector<GH>& gh, std::vector<int>&
   }
   for (int depth = 0; depth <= max_depth && !level.empty(); ++depth) {
     std::vector<Work> next;
-    // colsample_bylevel
-    std::vector<int> lfeats = feats;
-    if (p.colsample_bylevel < 1.0 && (int)lfeats.size() > 1) {
-      int m = (int)lfeats.size();
-      int k = std::max(1, (int)std::floor(p.colsample_bylevel * m + 1e-9));
-      Rng lrng(splitmix(level_key ^ splitmix((uint64_t)depth + 1)));
-      for (int i = 0; i < m; ++i) std::swap(lfeats[i], lfeats[i + (int)(lrng.next() % (uint64_t)(m - i))]);
-      lfeats.resize(k);
-    }
+    const std::vector<int> lfeats = level_features(feats, draws.level_key, depth, p);   // colsample_bylevel
     for (Work& w : level) {
       Node& nd = tree.nodes[w.node];
       nd.value = calc_weight(p, w.G, w.H) * p.eta;
@@ -301,8 +237,7 @@ double auc_score(const std::vector<double>& s, const std::vector<double>& y) {
     for (size_t k = i; k <= j; ++k) if (y[idx[k]] > 0.5) { rank_sum += avg_rank; npos += 1; } else nneg += 1;
     i = j + 1;
   }
-  if (npos == 0 || nneg == 0) return 0.5;
-  return (rank_sum - npos * (npos + 1) / 2) / (npos * nneg);
+  return auc_from_rank_sum(rank_sum, npos, nneg);
 }
 
 double eval_metric(int metric, int obj, int K, const std::vector<int>& rows, const std::vector<double>& margin,
@@ -362,8 +297,6 @@ double eval_metric(int metric, int obj, int K, const std::vector<int>& rows, con
   return 0.0;
 }
 
-bool higher_better(int metric) { return metric == M_AUC; }
-
 }  // namespace
 
 extern "C" {
@@ -388,29 +321,21 @@ int gbdt_cv(const float* X, int n, int F, const float* y, const int* fold_of, in
   const int K = multi ? std::max(2, num_class) : 1;
   Quantized q = quantize(X, n, F);
   std::vector<FoldState> folds(nfold);
-  double base_margin = p.base_score;
-  if (objective == OBJ_LOGISTIC || objective == OBJ_BINARY_LOGISTIC) {
-    const double b = std::min(1 - 1e-7, std::max(1e-7, p.base_score));
-    base_margin = std::log(b / (1 - b));
-  }
   for (int k = 0; k < nfold; ++k) {
     for (int i = 0; i < n; ++i) (fold_of[i] == k ? folds[k].test : folds[k].train).push_back(i);
-    folds[k].margin.assign((size_t)n * K, base_margin);
+    folds[k].margin.assign((size_t)n * K, base_margin(objective, p.base_score));
   }
   if (nthreads <= 0) nthreads = (int)std::max(1u, std::thread::hardware_concurrency());
-  const int eval_metric_id = metrics[n_metrics - 1];
-  double best_score = higher_better(eval_metric_id) ? -INFINITY : INFINITY;
-  int best_round = 0, rounds_done = 0;
-  std::vector<double> train_vals((size_t)nfold * n_metrics), test_vals((size_t)nfold * n_metrics);
+  EarlyStop stop(metrics[n_metrics - 1], early_stopping_rounds);     // the last metric decides
+  int rounds_done = 0;
+  std::vector<double> train_vals((size_t)n_metrics * nfold), test_vals((size_t)n_metrics * nfold);   // [metric][fold]
 
   auto round_fold = [&](int k, int round) {
     FoldState& fs = folds[k];
-    const uint64_t fold_round = splitmix(seed ^ splitmix((uint64_t)k * 1000003ull + (uint64_t)round * 7919ull + 17));
+    const uint64_t fold_round = fold_round_seed(seed, k, round);
     for (int c = 0; c < K; ++c) {
-      // one stream per tree (class c of fold k, round): a fixed number of draws
-      // per tree (row key, colsample_bytree, level key), so the GPU engine
-      // (csrc/hip/gbdt_hist.hip) derives every tree's draws up front
-      Rng rng(c == 0 ? fold_round : splitmix(fold_round ^ splitmix((uint64_t)c * 0x51ED27ull + 3)));
+      Rng rng(class_stream(fold_round, c));
+      const TreeDraws draws = draw_tree(rng, p, F);
       std::vector<GH> gh(n, GH{0.0, 0.0});
       for (int i : fs.train) {
         const double* m = &fs.margin[(size_t)i * K];
@@ -433,19 +358,17 @@ int gbdt_cv(const float* X, int n, int F, const float* y, const int* fold_of, in
       std::vector<int> rows;
       rows.reserve(fs.train.size());
       if (p.subsample < 1.0) {
-        // counter-based Bernoulli per row, keyed by one draw of the stream: the
-        // GPU path (csrc/hip/gbdt_hist.hip root_rows_kernel) samples the same rows in parallel
-        const uint64_t key = rng.next();
-        for (int i : fs.train) if (row_uniform(key, (uint64_t)i) < p.subsample) rows.push_back(i);
+        // the GPU path (csrc/hip/gbdt_hist.hip root_rows_kernel) samples the same rows in parallel
+        for (int i : fs.train) if (row_uniform(draws.row_key, (uint64_t)i) < p.subsample) rows.push_back(i);
       } else {
         rows = fs.train;
       }
-      Tree t = build_tree(q, gh, rows, p, rng);
+      Tree t = build_tree(q, gh, rows, p, draws);
       for (int i = 0; i < n; ++i) fs.margin[(size_t)i * K + c] += t.predict(&q.bins[(size_t)i * F]);
     }
     for (int m = 0; m < n_metrics; ++m) {
-      train_vals[(size_t)k * n_metrics + m] = eval_metric(metrics[m], objective, K, fs.train, fs.margin, y);
-      test_vals[(size_t)k * n_metrics + m] = eval_metric(metrics[m], objective, K, fs.test, fs.margin, y);
+      train_vals[(size_t)m * nfold + k] = eval_metric(metrics[m], objective, K, fs.train, fs.margin, y);
+      test_vals[(size_t)m * nfold + k] = eval_metric(metrics[m], objective, K, fs.test, fs.margin, y);
     }
   };
 
@@ -460,25 +383,13 @@ int gbdt_cv(const float* X, int n, int F, const float* y, const int* fold_of, in
     } else {
       for (int k = 0; k < nfold; ++k) round_fold(k, round);
     }
-    for (int m = 0; m < n_metrics; ++m) {
-      double trm = 0, tem = 0;
-      for (int k = 0; k < nfold; ++k) { trm += train_vals[(size_t)k * n_metrics + m]; tem += test_vals[(size_t)k * n_metrics + m]; }
-      trm /= nfold; tem /= nfold;
-      double trs = 0, tes = 0;
-      for (int k = 0; k < nfold; ++k) {
-        const double a = train_vals[(size_t)k * n_metrics + m] - trm, b = test_vals[(size_t)k * n_metrics + m] - tem;
-        trs += a * a; tes += b * b;
-      }
-      double* o = &out_hist[((size_t)round * n_metrics + m) * 4];
-      o[0] = trm; o[1] = std::sqrt(trs / nfold); o[2] = tem; o[3] = std::sqrt(tes / nfold);
-    }
+    for (int m = 0; m < n_metrics; ++m)
+      write_fold_stats(&train_vals[(size_t)m * nfold], &test_vals[(size_t)m * nfold], nfold,
+                       &out_hist[((size_t)round * n_metrics + m) * 4]);
     rounds_done = round + 1;
-    const double score = out_hist[((size_t)round * n_metrics + (n_metrics - 1)) * 4 + 2];
-    const bool better = higher_better(eval_metric_id) ? score > best_score : score < best_score;
-    if (better) { best_score = score; best_round = round; }
-    if (early_stopping_rounds > 0 && round - best_round >= early_stopping_rounds) break;
+    if (stop.update(round, out_hist[((size_t)round * n_metrics + (n_metrics - 1)) * 4 + 2])) break;
   }
-  return early_stopping_rounds > 0 ? best_round + 1 : rounds_done;
+  return stop.kept_rows(rounds_done);
 }
 
 // Quantise only (exposed for the HIP path and tests): bins out [n][F], nbins out [F].

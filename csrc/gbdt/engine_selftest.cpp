@@ -8,7 +8,8 @@
 // and run without Python in the process, so every report is the engine's.
 // It walks the code paths the GA reaches: every objective family, every
 // metric, row / column sampling, L1 / max_delta_step / gamma, early stopping,
-// tiny folds (empty leaves) and both quantiser layouts.
+// tiny folds (empty leaves) and both quantiser layouts. Then it checks
+// cv_protocol.h, what the CPU and the GPU engine share, directly.
 
 #include <cmath>
 #include <cstdint>
@@ -16,6 +17,8 @@
 #include <cstring>
 #include <random>
 #include <vector>
+
+#include "cv_protocol.h"
 
 extern "C" {
 int gbdt_cv(const float* X, int n, int F, const float* y, const int* fold_of, int nfold, const double* params,
@@ -75,9 +78,89 @@ int run(const Data& d, int nfold, const double* p, int obj, int ncls, std::vecto
   return kept;
 }
 
+bool subset(const std::vector<int>& a, const std::vector<int>& of) {
+  for (int v : a)
+    if (std::find(of.begin(), of.end(), v) == of.end()) return false;
+  return true;
+}
+
+// the sampling draws: F = 7, colsample_bytree 0.6 -> 4 features, colsample_bylevel 0.5 -> 2 of them per level
+void protocol_sampling() {
+  using namespace gbdt;
+  Params p;
+  std::memcpy(&p, P_default, sizeof p);
+  p.colsample_bytree = 0.6; p.colsample_bylevel = 0.5;
+  const int F = 7;
+  Rng a(42), b(42);
+  const std::vector<int> ta = tree_features(a, p, F), tb = tree_features(b, p, F);
+  const uint64_t ka = a.next(), kb = b.next();
+  check(ta == tb && ka == kb, "same seed, same tree features and level key");
+  check((int)ta.size() == std::max(1, (int)std::floor(0.6 * F + 1e-9)) && ta.size() == 4, "tree list size");
+  check(std::is_sorted(ta.begin(), ta.end()) && std::adjacent_find(ta.begin(), ta.end()) == ta.end() &&
+            ta.front() >= 0 && ta.back() < F, "tree list: distinct features, ascending");
+  for (int d = 0; d <= 3; ++d) {
+    const std::vector<int> la = level_features(ta, ka, d, p);
+    check((int)la.size() == std::max(1, (int)std::floor(0.5 * ta.size() + 1e-9)) && la.size() == 2, "level list size");
+    check(subset(la, ta) && la[0] != la[1], "level list is a subset of the tree list");
+    check(la == level_features(tb, kb, d, p), "same seed, same level list");
+  }
+  p.colsample_bylevel = 1.0;
+  check(level_features(ta, 0, 2, p) == ta, "no level sampling: the tree list");
+  p.colsample_bylevel = 0.5;
+  // the row key is the stream's first draw, and only with subsample < 1
+  Rng r0(42), r1(42);
+  const TreeDraws t0 = draw_tree(r0, p, F);
+  p.subsample = 0.7;
+  const TreeDraws t1 = draw_tree(r1, p, F);
+  check(t0.row_key == 0 && t0.feats == ta && t0.level_key == ka, "draw_tree without subsample: features, then level key");
+  check(t1.row_key != 0 && (t1.feats != t0.feats || t1.level_key != t0.level_key), "the row key draw shifts the stream");
+  const double u = row_uniform(t1.row_key, 5);
+  check(u >= 0.0 && u < 1.0 && u == row_uniform(t1.row_key, 5) && u != row_uniform(t1.row_key, 6), "row_uniform");
+}
+
+void protocol_stats_and_stopping() {
+  using namespace gbdt;
+  const double tr[3] = {1.0, 2.0, 3.0}, te[3] = {0.5, 0.5, 2.0};
+  double o[4];
+  write_fold_stats(tr, te, 3, o);      // population std: sqrt(2 / 3), sqrt((0.25 + 0.25 + 1) / 3)
+  check(o[0] == 2.0 && std::fabs(o[1] - std::sqrt(2.0 / 3.0)) < 1e-15, "train mean / std");
+  check(o[2] == 1.0 && std::fabs(o[3] - std::sqrt(0.5)) < 1e-15, "test mean / std");
+  {
+    EarlyStop s(M_RMSE, 2);           // best at round 1; the tie at round 3 does not move it
+    const double v[5] = {1.0, 0.8, 0.9, 0.8, 0.7};
+    int r = 0;
+    while (r < 5 && !s.update(r, v[r])) ++r;
+    check(r == 3 && s.kept_rows(r + 1) == 2, "early stopping, lower is better");
+  }
+  {
+    EarlyStop s(M_AUC, 2);            // auc is maximised
+    const double v[5] = {0.6, 0.7, 0.7, 0.65, 0.9};
+    int r = 0;
+    while (r < 5 && !s.update(r, v[r])) ++r;
+    check(r == 3 && s.kept_rows(r + 1) == 2, "early stopping, auc");
+  }
+  {
+    EarlyStop s(M_RMSE, 0);           // off: every round is kept
+    bool stopped = false;
+    for (int r = 0; r < 5; ++r) stopped = stopped || s.update(r, 5.0 - r + (r == 2 ? 9.0 : 0.0));
+    check(!stopped && s.kept_rows(5) == 5, "early stopping off");
+  }
+  check(higher_better(M_AUC) && !higher_better(M_LOGLOSS), "higher_better");
+  check(auc_from_rank_sum(7.0, 2, 2) == 1.0 && auc_from_rank_sum(3.0, 2, 2) == 0.0, "auc from rank sum");
+  check(auc_from_rank_sum(3.0, 2, 0) == 0.5 && auc_from_rank_sum(0.0, 0, 4) == 0.5, "auc with one class");
+  for (int obj = 0; obj <= 5; ++obj) {
+    const bool logit = obj == OBJ_LOGISTIC || obj == OBJ_BINARY_LOGISTIC;
+    check(base_margin(obj, 0.3) == (logit ? std::log(0.3 / 0.7) : 0.3), "base margin");
+    check(base_margin(obj, 0.0) == (logit ? std::log(1e-7 / (1 - 1e-7)) : 0.0), "base score clamped from below");
+    check(base_margin(obj, 1.0) == (logit ? std::log((1 - 1e-7) / (1 - (1 - 1e-7))) : 1.0), "base score clamped from above");
+  }
+}
+
 }  // namespace
 
 int main() {
+  protocol_sampling();
+  protocol_stats_and_stopping();
   // quantiser, both layouts
   {
     Data d = make(5000, 13, 0, 5, 1);

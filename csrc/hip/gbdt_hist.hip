@@ -33,7 +33,7 @@
 // metric read-back that early stopping needs. The per-tree random draws
 // (row-subsample key, colsample_bytree / _bylevel feature orders) do not
 // depend on the data, so the host derives them up front (same streams as the
-// CPU engine, csrc/gbdt/engine.cpp round_fold / build_tree) and uploads them
+// CPU engine: csrc/gbdt/cv_protocol.h draw_tree) and uploads them
 // with one asynchronous copy per round.
 //
 // Histograms are fixed point: every row's (g, h) is scaled by a power of two
@@ -60,6 +60,7 @@
 #include <vector>
 
 #include "gbdt_cache.h"
+#include "../gbdt/cv_protocol.h"
 
 #define GB_BINS 256
 // features per histogram workgroup: gradient-only packed image (constant hessian) / (g, h) pairs
@@ -75,32 +76,14 @@
 #define GB_MAXD 12       // deepest supported tree
 
 namespace {
+using namespace gbdt;
 typedef long long i64;
 typedef unsigned long long u64;
 
+// the kernels' share of Params, same field names (cv_protocol.h calc_weight / calc_gain)
 struct DevParams {
   double min_child_weight, lambda, alpha, max_delta_step, eta, gamma;
 };
-
-__device__ __forceinline__ double thr_l1(double g, double a) { return g > a ? g - a : (g < -a ? g + a : 0.0); }
-
-__device__ __forceinline__ double dev_weight(const DevParams& p, double G, double H) {
-  if (H < p.min_child_weight || H <= 0.0) return 0.0;
-  double w = -thr_l1(G, p.alpha) / (H + p.lambda);
-  if (p.max_delta_step != 0.0 && fabs(w) > p.max_delta_step) w = copysign(p.max_delta_step, w);
-  return w;
-}
-
-__device__ __forceinline__ double dev_gain(const DevParams& p, double G, double H) {
-  if (H < p.min_child_weight || H <= 0.0) return 0.0;
-  if (p.max_delta_step == 0.0) {
-    const double t = thr_l1(G, p.alpha);
-    return t * t / (H + p.lambda);
-  }
-  const double w = dev_weight(p, G, H);
-  const double r = -(2.0 * G * w + (H + p.lambda) * w * w);
-  return p.alpha == 0.0 ? r : r + p.alpha * fabs(w);
-}
 
 // one node of a level (per fold): row segment [start, start + count) in the
 // level's row list; exact fixed-point totals; built = histogram from rows
@@ -184,7 +167,7 @@ __device__ __forceinline__ int fx_exp(unsigned int maxbits, int lg_n) {
 }
 
 // root rows of fold k: rows of the other folds, Bernoulli(subsample) by the
-// counter-based hash of the CPU engine (engine.cpp row_uniform) keyed by one
+// counter-based hash of the CPU engine (cv_protocol.h row_uniform) keyed by one
 // draw of the tree's stream. Unordered compaction with ONE cursor atomic per
 // workgroup and 4096 rows (a per-wave atomic on the fold's single counter
 // serialised at L2: 0.9 ms per fold at 1M rows)
@@ -203,13 +186,8 @@ __global__ void __launch_bounds__(256) root_rows_kernel(const int* __restrict__ 
     for (int j = 0; j < RR_PER; ++j) {
       const long i = s0 + (long)j * 256 + tid;
       bool keep = i < n && fold_of[i] != k;
-      if (keep && subsample < 1.0) {
-        u64 x = (u64)i + 0x9E3779B97F4A7C15ull;
-        x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull; x = (x ^ (x >> 27)) * 0x94D049BB133111EBull; x ^= x >> 31;
-        x = (key ^ x) + 0x9E3779B97F4A7C15ull;
-        x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull; x = (x ^ (x >> 27)) * 0x94D049BB133111EBull; x ^= x >> 31;
-        keep = (double)(x >> 11) * (1.0 / 9007199254740992.0) < subsample;
-      }
+      if (keep && subsample < 1.0) keep = row_uniform(key, (u64)i) < subsample;
+
       if (keep) keepm |= 1u << j;
     }
     const int cnt = __popc(keepm);
@@ -494,7 +472,7 @@ __global__ void __launch_bounds__(64) split_kernel(Geo geo, int depth, const i64
     }
     i64 GLf = pg - sg, HLf = ph - sh;           // exclusive prefix
     const double G = (double)nd.G * ig, H = (double)nd.H * ih;
-    const double parent = dev_gain(p, G, H);
+    const double parent = calc_gain(p, G, H);
     const int nb = nbins[f];
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
@@ -504,7 +482,7 @@ __global__ void __launch_bounds__(64) split_kernel(Geo geo, int depth, const i64
       const double GL = (double)GLf * ig, HL = (double)HLf * ih;
       const double GR = G - GL, HR = H - HL;
       if (HL < p.min_child_weight || HR < p.min_child_weight || HL <= 0.0 || HR <= 0.0) continue;
-      const double chg = dev_gain(p, GL, HL) + dev_gain(p, GR, HR) - parent;
+      const double chg = calc_gain(p, GL, HL) + calc_gain(p, GR, HR) - parent;
       if (chg > bg + 1e-12 || (bb < 0 && chg > 1e-12)) { bg = chg; bb = b; bGL = GLf; bHL = HLf; }
     }
     for (int o = 1; o < 64; o <<= 1) {          // combine lane groups in bin (scan) order
@@ -575,7 +553,7 @@ __global__ void __launch_bounds__(256) plan_split_kernel(Geo geo, int depth, con
     bool split = false;
     NodeBest b{0.0, 0, 0, -1, -1};
     if (nd.exists) {
-      leaf[(size_t)k * tsz + id] = (float)(dev_weight(p, (double)nd.G * ig, (double)nd.H * ih) * p.eta);
+      leaf[(size_t)k * tsz + id] = (float)(calc_weight(p, (double)nd.G * ig, (double)nd.H * ih) * p.eta);
       tree[(size_t)k * tsz + id] = make_int2(-1, 0);
       if (depth < geo.max_depth && nd.count >= 2) {
         b = best[(size_t)k * geo.Lh + j];
@@ -818,7 +796,7 @@ __global__ void __launch_bounds__(256) predict_kernel(Geo geo, const uint8_t* __
 
 // ---- G8: metric partial sums over every fold's train / test rows -------------
 // out[(k * gridDim.x + block) * 4 + (train sum, train count, test sum, test count)];
-// metric 0 rmse, 1 mae, 2 logloss, 3 error, 5 merror, 6 mlogloss (engine.cpp eval_metric)
+// every Metric but M_AUC (engine.cpp eval_metric)
 __global__ void __launch_bounds__(256) metric_kernel(Geo geo, const float* __restrict__ margin,
                                                      const float* __restrict__ y, const int* __restrict__ fold_of,
                                                      int metric, int objective, double* __restrict__ out) {
@@ -830,20 +808,20 @@ __global__ void __launch_bounds__(256) metric_kernel(Geo geo, const float* __res
     const float* m = mk + (size_t)i * K;
     const float sig = 1.f / (1.f + expf(-m[0]));
     float v;
-    if (metric == 0 || metric == 1) {
-      const float d = ((objective == 1 || objective == 2) ? sig : m[0]) - y[i];
-      v = metric == 0 ? d * d : fabsf(d);
-    } else if (metric == 2) {
+    if (metric == M_RMSE || metric == M_MAE) {
+      const float d = ((objective == OBJ_LOGISTIC || objective == OBJ_BINARY_LOGISTIC) ? sig : m[0]) - y[i];
+      v = metric == M_RMSE ? d * d : fabsf(d);
+    } else if (metric == M_LOGLOSS) {
       const float pc = fminf(fmaxf(sig, 1e-15f), 1.f - 1e-15f);
       v = -(y[i] * logf(pc) + (1.f - y[i]) * logf(1.f - pc));
-    } else if (metric == 3) {
-      const bool pos = (objective == 3) ? (m[0] > 0.f) : (sig > 0.5f);
+    } else if (metric == M_ERROR) {
+      const bool pos = (objective == OBJ_BINARY_LOGITRAW) ? (m[0] > 0.f) : (sig > 0.5f);
       v = (pos != (y[i] > 0.5f)) ? 1.f : 0.f;
     } else {
       int arg = 0;
       float mxv = m[0];
       for (int q = 1; q < K; ++q) if (m[q] > mxv) { mxv = m[q]; arg = q; }
-      if (metric == 5) v = (arg != (int)y[i]) ? 1.f : 0.f;
+      if (metric == M_MERROR) v = (arg != (int)y[i]) ? 1.f : 0.f;
       else {
         float z = 0.f;
         for (int q = 0; q < K; ++q) z += expf(m[q] - mxv);
@@ -918,36 +896,23 @@ __global__ void __launch_bounds__(256) auc_rank_kernel(const u64* __restrict__ s
     if (s[t] != 0.0) atomicAdd(&acc[t], s[t]);
 }
 
-uint64_t smix(uint64_t x) {
-  x += 0x9E3779B97F4A7C15ull;
-  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-  return x ^ (x >> 31);
-}
-
-#define HC(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { rc = -100 - (int)e_; goto done; } } while (0)
-
 }  // namespace
-
-// feature-major copy of the cached bins (partition), rebuilt when the cache changes
-static uint8_t* g_binsT = nullptr;
-static const uint8_t* g_binsT_src = nullptr;
-static long long g_binsT_key = 0;
-static size_t g_binsT_bytes = 0;
 
 namespace gbdt_cache {
 uint8_t* bins = nullptr;
 long long key = 0;
 size_t bytes = 0;
 std::mutex mu;
-void invalidate_derived() { g_binsT_key = 0; }
+// feature-major copy of the cached bins (partition), rebuilt when the cache changes
+static struct { uint8_t* bins = nullptr; const uint8_t* src = nullptr; long long key = 0; size_t bytes = 0; } binsT;
+void invalidate_derived() { binsT.key = 0; }
 }  // namespace gbdt_cache
 
 // ---- stage trace (tests/test_gbdt_stages.py): with a sink, the host synchronises after the stage that
-// produces a buffer, copies it to a host vector and hands it to the sink. Every site is one
-// `if (sink && round < trace_rounds && (trace_mask & TAG))`: with a null sink (gbdt_cv_hip) no launch, copy or
-// synchronisation is added. Per-tree and per-round blocks carry depth -1 (the margins before the tree's
-// gradients: -2).
+// produces a buffer, copies it to a host vector and hands it to the sink. Every site is one Tracer::emit,
+// which does the guard `sink && round < trace_rounds && (trace_mask & TAG)` itself: with a null sink
+// (gbdt_cv_hip) no launch, copy or synchronisation is added. Per-tree and per-round blocks carry depth -1 (the
+// margins before the tree's gradients: -2).
 extern "C" typedef void (*gbdt_trace_fn)(void* user, int round, int cls, int depth, int tag, const void* host_data,
                                          long long bytes);
 enum : unsigned {
@@ -973,320 +938,275 @@ enum : unsigned {
   GT_AUC = 1u << 19,     // double [nfold][4]: train rank sum, train positives, test rank sum, test positives
 };
 
-extern "C" {
+namespace {
 
-// Same contract as gbdt_cv (csrc/gbdt/engine.cpp) for every objective
-// (reg:linear/squarederror, reg:logistic, binary:logistic/logitraw,
-// multi:softmax/softprob: one tree per class) and every metric (rmse, mae,
-// logloss, error, auc, merror, mlogloss; early stopping on the last, auc
-// maximised). auc needs nfold <= 32 (64 sort segments).
-// bins_h may be null when gbdt_quantize_hip already left the dataset's bins
-// on the device under cache_key (returns -7 if they were evicted). bins:
-// ROW-major [n][Fs] uint8 (Fs >= F, Fs % 4 == 0). cache_key != 0 keeps the
-// device copy of the bins across calls for the same key (one dataset, many
-// candidates).
-static int gbdt_cv_body(const uint8_t* bins_h, int Fs, const int* nbins_h, int n, int F, const float* y_h,
-                        const int* fold_h, int nfold, const double* P, int objective, int num_class,
-                        const int* metrics, int n_metrics, int num_boost_round, int early_stopping_rounds,
-                        unsigned long long seed, long long cache_key, double* out_hist, int trace_rounds,
-                        unsigned trace_mask, gbdt_trace_fn sink, void* user) {
-  if (objective < 0 || objective > 5 || n_metrics < 1 || Fs % 4 || Fs < F || n <= 0 || nfold <= 0 || F <= 0)
-    return -1;
-  bool want_auc = false;
-  for (int mi = 0; mi < n_metrics; ++mi) {
-    if (metrics[mi] < 0 || metrics[mi] > 6) return -1;
-    want_auc = want_auc || metrics[mi] == 4;
-  }
-  if (want_auc && nfold > 32) return -1;
-  const bool multi = objective >= 4;
-  const int K = multi ? std::max(2, num_class) : 1;
-  const int obj = multi ? 3 : (objective == 0 ? 0 : (objective == 1 ? 1 : 2));
-  // squared error: h = 1 for every row -> count histograms for the hessian (hist_kernel<true>)
-  const bool hconst = obj == 0;
-  const int D = std::max(0, std::min((int)P[2], GB_MAXD));
-  std::lock_guard<std::mutex> lock(gbdt_cache::mu);   // one GBDT call at a time per process (bins cache)
-  int rc = 0;
-  Geo geo;
-  geo.n = n; geo.F = F; geo.Fs = Fs; geo.nfold = nfold; geo.K = K; geo.max_depth = D;
-  geo.Lmax = 1 << D;
-  geo.Lh = 1 << std::max(0, D - 1);
-  // rows per histogram chunk: fewer, longer chunks = fewer partial slots for the reduce to sum
-  geo.rch = GB_R;
-  const int rchunks = (n + geo.rch - 1) / geo.rch;
-  geo.maxch = rchunks + geo.Lh + 2;
-  geo.maxslot = 2 * rchunks + 2;
-  geo.lg_n = 0;
-  while ((1ll << geo.lg_n) < (long long)n + 1) ++geo.lg_n;
-  if (hconst) geo.lg_n = std::max(geo.lg_n, 32);   // |qg| < 2^29 per row (packed counts)
-  const int tsz = (2 << D) - 1;
-  const size_t per_node = (size_t)F * 2 * GB_BINS;      // int64 per histogram node
-  DevParams dp{P[1], P[8], P[9], P[4], P[0], P[3]};
-  const int blocks = std::min(2048, (n + 255) / 256);
-  const int pblocks = (n + 256 * PT_PER - 1) / (256 * PT_PER);
-  const int mblocks = std::min(blocks, 256);
-  // predict: R staged rows (a power of two, 32 KB of LDS) + as many folds' trees as fit 96 KB more
-  int pr_rows = 0;
-  if (Fs + 4 <= 32768 / 4) {
-    pr_rows = 256;
-    while (pr_rows > 4 && (size_t)pr_rows * (Fs + 4) > 32768) pr_rows >>= 1;
-  }
-  const int pk = (int)std::max<size_t>(1, std::min<size_t>(nfold, (96u << 10) / ((size_t)tsz * 12)));
-  const size_t pred_lds = (size_t)pr_rows * (Fs + 4) + 8 + (size_t)pk * tsz * 12;
-  if (pred_lds > 65536)
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(predict_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)pred_lds);
-  const int nfb = hconst ? (F + HB_FC - 1) / HB_FC : (F + HB_FG - 1) / HB_FG;
-  const int ylen = std::max(1, (int)(per_node / 4096));
-  const int rlen = std::max(1, (int)(per_node / 512));       // reduce: 2 elements per thread, ~256 workgroups per node
-  // device buffers
-  float *d_y = nullptr, *d_margin = nullptr, *d_leaf = nullptr;
-  int *d_fold = nullptr, *d_nb = nullptr, *d_rows[2] = {nullptr, nullptr}, *d_order = nullptr, *d_counts = nullptr,
-      *d_nroot = nullptr;
-  float2* d_gh = nullptr;
-  i64 *d_hist[2] = {nullptr, nullptr}, *d_part = nullptr;
-  LNode* d_lvl[2] = {nullptr, nullptr};
-  Chunk* d_chunks = nullptr;
-  Red* d_reds = nullptr;
-  SplitOut* d_cand = nullptr;
-  NodeBest* d_best = nullptr;
-  int2 *d_tree = nullptr, *d_split = nullptr, *d_cur = nullptr;
-  unsigned int* d_mx = nullptr;
-  u64* d_keys = nullptr;
-  double* d_met = nullptr;
-  void* h_up = nullptr;           // pinned upload block: keys [K][nfold] u64, orders [K][nfold][D+1][F] int
-  double* h_met = nullptr;        // pinned metric read-back
-  const size_t keys_bytes = sizeof(u64) * K * nfold;
-  const size_t order_elems = (size_t)nfold * (D + 1) * F;
-  const size_t up_bytes = keys_bytes + sizeof(int) * K * order_elems;
-  const size_t met_elems = (size_t)n_metrics * nfold * mblocks * 4;
-  const uint8_t* d_bins = nullptr;
-  double base = P[11];
-  const bool lower_better = metrics[n_metrics - 1] != 4;      // engine.cpp higher_better: auc
-  double best_score = lower_better ? INFINITY : -INFINITY;
-  // auc: sort keys (two buffers + rocprim scratch) and [2 nfold][2] rank sums; rows per test fold
-  u64 *d_akeys = nullptr, *d_asorted = nullptr;
-  void* d_atmp = nullptr;
-  size_t atmp_bytes = 0;
-  double* d_aacc = nullptr;
-  const size_t aN = (size_t)nfold * n;
-  const int aseg_bits = 33 + [](int s) { int b = 0; while ((1 << b) < s) ++b; return b; }(2 * nfold);
-  std::vector<double> h_aacc(4 * (size_t)nfold);
-  std::vector<double> ntest(nfold, 0.0);
-  for (int i = 0; i < n; ++i)
-    if (fold_h[i] >= 0 && fold_h[i] < nfold) ntest[fold_h[i]] += 1.0;
-  int best_round = 0, rounds_done = 0;
-  static const bool timing = std::getenv("GENTUN_GBDT_TIMING") != nullptr;
-  static const int progress = std::getenv("GENTUN_GBDT_PROGRESS") ? std::atoi(std::getenv("GENTUN_GBDT_PROGRESS")) : 0;
-  const auto t_start = std::chrono::steady_clock::now();
-  // trace: wait for the stage, copy its buffer(s) to the host, hand them to the sink as one block
-  auto emit = [&](int round, int cls, int depth, unsigned tag, const void* dev, size_t bytes,
-                  const void* dev2 = nullptr, size_t bytes2 = 0) -> hipError_t {
+#define HC(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return -100 - (int)e_; } while (0)
+
+struct Tracer {
+  gbdt_trace_fn sink; void* user; int trace_rounds; unsigned trace_mask;
+  bool on(int round, unsigned tag) const { return sink && round < trace_rounds && (trace_mask & tag); }
+  // wait for the stage, copy its buffer(s) to the host, hand them to the sink as one block
+  hipError_t emit(int round, int cls, int depth, unsigned tag, const void* dev, size_t bytes,
+                  const void* dev2 = nullptr, size_t bytes2 = 0) const {
+    if (!on(round, tag)) return hipSuccess;
     std::vector<char> h(bytes + bytes2);
     hipError_t e = hipStreamSynchronize(0);
     if (e == hipSuccess) e = hipMemcpy(h.data(), dev, bytes, hipMemcpyDeviceToHost);
     if (e == hipSuccess && bytes2) e = hipMemcpy(h.data() + bytes, dev2, bytes2, hipMemcpyDeviceToHost);
     if (e == hipSuccess) sink(user, round, cls, depth, (int)tag, h.data(), (long long)h.size());
     return e;
-  };
+  }
+  // a per-round block the host already holds
+  void emit_host(int round, unsigned tag, const void* host, size_t bytes) const {
+    if (on(round, tag)) sink(user, round, -1, -1, (int)tag, host, (long long)bytes);
+  }
+};
 
-  {
-    const size_t nbytes = (size_t)n * Fs;
-    if (cache_key == 0 || cache_key != gbdt_cache::key || gbdt_cache::bytes != nbytes || gbdt_cache::bins == nullptr) {
-      if (bins_h == nullptr) return -7;      // device copy evicted: the caller quantises again
-      if (gbdt_cache::bins) (void)hipFree(gbdt_cache::bins);
-      gbdt_cache::bins = nullptr; gbdt_cache::key = 0; gbdt_cache::bytes = 0;
-      if (hipMalloc(&gbdt_cache::bins, nbytes) != hipSuccess) return -100;
-      if (hipMemcpy(gbdt_cache::bins, bins_h, nbytes, hipMemcpyHostToDevice) != hipSuccess) return -100;
-      gbdt_cache::key = cache_key; gbdt_cache::bytes = nbytes;
+// hands out the device and pinned allocations of one CV call and frees them all when the call returns
+struct Workspace {
+  std::vector<void*> dev, pinned;
+  template <class T> hipError_t alloc(T*& p, size_t bytes) {
+    const hipError_t e = hipMalloc(&p, bytes);
+    if (e == hipSuccess) dev.push_back(p);
+    return e;
+  }
+  template <class T> hipError_t alloc_pinned(T*& p, size_t bytes) {
+    const hipError_t e = hipHostMalloc((void**)&p, bytes, hipHostMallocDefault);
+    if (e == hipSuccess) pinned.push_back(p);
+    return e;
+  }
+  Workspace() = default; Workspace(const Workspace&) = delete;
+  ~Workspace() { for (void* p : dev) (void)hipFree(p); for (void* p : pinned) (void)hipHostFree(p); }
+};
+
+// The dataset's bins on the device (gbdt_cache::bins), kept under cache_key across calls, and their feature-major
+// copy (binsT.bins). -7: bins_h is null and the device copy was evicted (the caller quantises again).
+int ensure_bins(const uint8_t* bins_h, int n, int Fs, long long cache_key) {
+  auto& T = gbdt_cache::binsT;
+  const size_t nbytes = (size_t)n * Fs;
+  if (cache_key == 0 || cache_key != gbdt_cache::key || gbdt_cache::bytes != nbytes || gbdt_cache::bins == nullptr) {
+    if (bins_h == nullptr) return -7;
+    if (gbdt_cache::bins) (void)hipFree(gbdt_cache::bins);
+    gbdt_cache::bins = nullptr; gbdt_cache::key = 0; gbdt_cache::bytes = 0;
+    if (hipMalloc(&gbdt_cache::bins, nbytes) != hipSuccess) return -100;
+    if (hipMemcpy(gbdt_cache::bins, bins_h, nbytes, hipMemcpyHostToDevice) != hipSuccess) return -100;
+    gbdt_cache::key = cache_key; gbdt_cache::bytes = nbytes;
+  }
+  if (T.bins == nullptr || T.key == 0 || T.key != gbdt_cache::key || T.src != gbdt_cache::bins || T.bytes != nbytes) {
+    if (T.bins) { (void)hipFree(T.bins); T.bins = nullptr; }
+    if (hipMalloc(&T.bins, nbytes) != hipSuccess) return -100;
+    hipLaunchKernelGGL(transpose_bins_kernel, dim3((n + 63) / 64, (Fs + 63) / 64), dim3(256), 0, 0, gbdt_cache::bins,
+                       T.bins, n, Fs);
+    T.src = gbdt_cache::bins; T.key = gbdt_cache::key; T.bytes = nbytes;
+  }
+  return 0;
+}
+
+// One CV call: geometry, launch shapes, buffers and the steps of a round (each returns 0 or -100 - hipError)
+struct CvRun {
+  Params p; int objective, n_metrics; const int* metrics; u64 seed; Tracer tr;
+  int n, F, Fs, nfold, K, D;
+  int obj;                 // grad_kernel's code: 0 squared error, 1 reg:logistic, 2 binary, 3 multi-class
+  bool hconst, want_auc;   // hconst: h = 1 for every row -> count histograms for the hessian (hist_kernel<true>)
+  Geo geo; DevParams dp;
+  int tsz, blocks, pblocks, mblocks, pr_rows, pk, nfb, ylen, rlen, aseg_bits;
+  size_t per_node, pred_lds, keys_bytes, order_elems, met_elems, aN, atmp_bytes = 0;
+  Workspace ws;
+  const uint8_t *d_bins, *d_binsT;
+  float *d_y, *d_margin, *d_leaf;
+  int *d_fold, *d_nb, *d_rows[2], *d_order, *d_counts, *d_nroot;
+  float2* d_gh; i64 *d_hist[2], *d_part; LNode* d_lvl[2]; Chunk* d_chunks; Red* d_reds;
+  SplitOut* d_cand; NodeBest* d_best; int2 *d_tree, *d_split, *d_cur; unsigned int* d_mx; u64* d_keys; double* d_met;
+  u64 *d_akeys, *d_asorted; void* d_atmp; double* d_aacc;   // auc: sort keys + rocprim scratch, [2 nfold][2] rank sums
+  char* h_up;                          // pinned upload block: keys [K][nfold] u64, orders [K][nfold][D+1][F] int
+  double* h_met;                       // pinned metric read-back
+  std::vector<double> h_aacc, ntest;   // ntest: rows per test fold
+
+  void shape(int n_, int F_, int Fs_, int nfold_, int num_class, const int* fold_h) {
+    n = n_; F = F_; Fs = Fs_; nfold = nfold_;
+    const bool multi = objective == OBJ_MULTI_SOFTMAX || objective == OBJ_MULTI_SOFTPROB;
+    K = multi ? std::max(2, num_class) : 1;
+    obj = multi ? 3 : (objective == OBJ_SQUARED ? 0 : (objective == OBJ_LOGISTIC ? 1 : 2));
+    hconst = obj == 0;
+    D = std::max(0, std::min((int)p.max_depth, GB_MAXD));
+    geo.n = n; geo.F = F; geo.Fs = Fs; geo.nfold = nfold; geo.K = K; geo.max_depth = D;
+    geo.Lmax = 1 << D; geo.Lh = 1 << std::max(0, D - 1);
+    // rows per histogram chunk: fewer, longer chunks = fewer partial slots for the reduce to sum
+    geo.rch = GB_R;
+    const int rchunks = (n + geo.rch - 1) / geo.rch;
+    geo.maxch = rchunks + geo.Lh + 2; geo.maxslot = 2 * rchunks + 2;
+    geo.lg_n = 0;
+    while ((1ll << geo.lg_n) < (long long)n + 1) ++geo.lg_n;
+    if (hconst) geo.lg_n = std::max(geo.lg_n, 32);   // |qg| < 2^29 per row (packed counts)
+    tsz = (2 << D) - 1;
+    per_node = (size_t)F * 2 * GB_BINS;      // int64 per histogram node
+    dp = DevParams{p.min_child_weight, p.lambda, p.alpha, p.max_delta_step, p.eta, p.gamma};
+    blocks = std::min(2048, (n + 255) / 256);
+    pblocks = (n + 256 * PT_PER - 1) / (256 * PT_PER);
+    mblocks = std::min(blocks, 256);
+    // predict: R staged rows (a power of two, 32 KB of LDS) + as many folds' trees as fit 96 KB more
+    pr_rows = 0;
+    if (Fs + 4 <= 32768 / 4) {
+      pr_rows = 256;
+      while (pr_rows > 4 && (size_t)pr_rows * (Fs + 4) > 32768) pr_rows >>= 1;
     }
-    d_bins = gbdt_cache::bins;
-    if (g_binsT == nullptr || g_binsT_key == 0 || g_binsT_key != gbdt_cache::key || g_binsT_src != d_bins ||
-        g_binsT_bytes != nbytes) {
-      if (g_binsT) (void)hipFree(g_binsT);
-      g_binsT = nullptr;
-      if (hipMalloc(&g_binsT, nbytes) != hipSuccess) return -100;
-      hipLaunchKernelGGL(transpose_bins_kernel, dim3((n + 63) / 64, (Fs + 63) / 64), dim3(256), 0, 0, d_bins, g_binsT,
-                         n, Fs);
-      g_binsT_src = d_bins; g_binsT_key = gbdt_cache::key; g_binsT_bytes = nbytes;
+    pk = (int)std::max<size_t>(1, std::min<size_t>(nfold, (96u << 10) / ((size_t)tsz * 12)));
+    pred_lds = (size_t)pr_rows * (Fs + 4) + 8 + (size_t)pk * tsz * 12;
+    if (pred_lds > 65536)
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(predict_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)pred_lds);
+    nfb = hconst ? (F + HB_FC - 1) / HB_FC : (F + HB_FG - 1) / HB_FG;
+    ylen = std::max(1, (int)(per_node / 4096));
+    rlen = std::max(1, (int)(per_node / 512));       // reduce: 2 elements per thread, ~256 workgroups per node
+    keys_bytes = sizeof(u64) * K * nfold; order_elems = (size_t)nfold * (D + 1) * F;
+    met_elems = (size_t)n_metrics * nfold * mblocks * 4; aN = (size_t)nfold * n;
+    aseg_bits = 33;
+    while ((1 << (aseg_bits - 33)) < 2 * nfold) ++aseg_bits;
+    h_aacc.assign(4 * (size_t)nfold, 0.0);
+    ntest.assign(nfold, 0.0);
+    for (int i = 0; i < n; ++i)
+      if (fold_h[i] >= 0 && fold_h[i] < nfold) ntest[fold_h[i]] += 1.0;
+  }
+
+  int allocate(const float* y_h, const int* fold_h, const int* nbins_h) {
+    HC(ws.alloc(d_y, sizeof(float) * n));
+    HC(ws.alloc(d_fold, sizeof(int) * n));
+    HC(ws.alloc(d_nb, sizeof(int) * F));
+    for (int b = 0; b < 2; ++b) HC(ws.alloc(d_rows[b], sizeof(int) * (size_t)nfold * n));
+    HC(ws.alloc(d_margin, sizeof(float) * (size_t)nfold * n * K));
+    HC(ws.alloc(d_gh, sizeof(float2) * (size_t)nfold * n));
+    for (int b = 0; b < 2; ++b) HC(ws.alloc(d_hist[b], sizeof(i64) * (size_t)nfold * geo.Lh * per_node));
+    HC(ws.alloc(d_part, sizeof(i64) * (size_t)nfold * geo.maxslot * per_node));
+    for (int b = 0; b < 2; ++b) HC(ws.alloc(d_lvl[b], sizeof(LNode) * (size_t)nfold * geo.Lmax));
+    HC(ws.alloc(d_chunks, sizeof(Chunk) * (size_t)nfold * geo.maxch));
+    HC(ws.alloc(d_reds, sizeof(Red) * (size_t)nfold * geo.maxch));
+    HC(ws.alloc(d_counts, sizeof(int) * 2 * nfold));
+    HC(ws.alloc(d_nroot, sizeof(int) * nfold));
+    HC(ws.alloc(d_cand, sizeof(SplitOut) * (size_t)nfold * geo.Lh * F));
+    HC(ws.alloc(d_best, sizeof(NodeBest) * (size_t)nfold * geo.Lh));
+    HC(ws.alloc(d_tree, sizeof(int2) * (size_t)nfold * tsz));
+    HC(ws.alloc(d_leaf, sizeof(float) * (size_t)nfold * tsz));
+    HC(ws.alloc(d_split, sizeof(int2) * (size_t)nfold * geo.Lmax));
+    HC(ws.alloc(d_cur, sizeof(int2) * (size_t)nfold * geo.Lmax));
+    HC(ws.alloc(d_mx, sizeof(unsigned int) * 2 * nfold));
+    HC(ws.alloc(d_keys, keys_bytes));
+    HC(ws.alloc(d_order, sizeof(int) * K * order_elems));
+    HC(ws.alloc(d_met, sizeof(double) * met_elems));
+    if (want_auc) {
+      HC(ws.alloc(d_akeys, sizeof(u64) * aN));
+      HC(ws.alloc(d_asorted, sizeof(u64) * aN));
+      HC(ws.alloc(d_aacc, sizeof(double) * 4 * nfold));
+      HC(rocprim::radix_sort_keys(nullptr, atmp_bytes, d_akeys, d_asorted, aN, 0u, (unsigned)aseg_bits));
+      HC(ws.alloc(d_atmp, std::max<size_t>(atmp_bytes, 1)));
     }
-  }
-  HC(hipMalloc(&d_y, sizeof(float) * n));
-  HC(hipMalloc(&d_fold, sizeof(int) * n));
-  HC(hipMalloc(&d_nb, sizeof(int) * F));
-  for (int b = 0; b < 2; ++b) HC(hipMalloc(&d_rows[b], sizeof(int) * (size_t)nfold * n));
-  HC(hipMalloc(&d_margin, sizeof(float) * (size_t)nfold * n * K));
-  HC(hipMalloc(&d_gh, sizeof(float2) * (size_t)nfold * n));
-  for (int b = 0; b < 2; ++b) HC(hipMalloc(&d_hist[b], sizeof(i64) * (size_t)nfold * geo.Lh * per_node));
-  HC(hipMalloc(&d_part, sizeof(i64) * (size_t)nfold * geo.maxslot * per_node));
-  for (int b = 0; b < 2; ++b) HC(hipMalloc(&d_lvl[b], sizeof(LNode) * (size_t)nfold * geo.Lmax));
-  HC(hipMalloc(&d_chunks, sizeof(Chunk) * (size_t)nfold * geo.maxch));
-  HC(hipMalloc(&d_reds, sizeof(Red) * (size_t)nfold * geo.maxch));
-  HC(hipMalloc(&d_counts, sizeof(int) * 2 * nfold));
-  HC(hipMalloc(&d_nroot, sizeof(int) * nfold));
-  HC(hipMalloc(&d_cand, sizeof(SplitOut) * (size_t)nfold * geo.Lh * F));
-  HC(hipMalloc(&d_best, sizeof(NodeBest) * (size_t)nfold * geo.Lh));
-  HC(hipMalloc(&d_tree, sizeof(int2) * (size_t)nfold * tsz));
-  HC(hipMalloc(&d_leaf, sizeof(float) * (size_t)nfold * tsz));
-  HC(hipMalloc(&d_split, sizeof(int2) * (size_t)nfold * geo.Lmax));
-  HC(hipMalloc(&d_cur, sizeof(int2) * (size_t)nfold * geo.Lmax));
-  HC(hipMalloc(&d_mx, sizeof(unsigned int) * 2 * nfold));
-  HC(hipMalloc(&d_keys, keys_bytes));
-  HC(hipMalloc(&d_order, sizeof(int) * K * order_elems));
-  HC(hipMalloc(&d_met, sizeof(double) * met_elems));
-  if (want_auc) {
-    HC(hipMalloc(&d_akeys, sizeof(u64) * aN));
-    HC(hipMalloc(&d_asorted, sizeof(u64) * aN));
-    HC(hipMalloc(&d_aacc, sizeof(double) * 4 * nfold));
-    HC(rocprim::radix_sort_keys(nullptr, atmp_bytes, d_akeys, d_asorted, aN, 0u, (unsigned)aseg_bits));
-    HC(hipMalloc(&d_atmp, std::max<size_t>(atmp_bytes, 1)));
-  }
-  HC(hipHostMalloc(&h_up, up_bytes, hipHostMallocDefault));
-  HC(hipHostMalloc((void**)&h_met, sizeof(double) * met_elems, hipHostMallocDefault));
-  HC(hipMemcpy(d_y, y_h, sizeof(float) * n, hipMemcpyHostToDevice));
-  HC(hipMemcpy(d_fold, fold_h, sizeof(int) * n, hipMemcpyHostToDevice));
-  HC(hipMemcpy(d_nb, nbins_h, sizeof(int) * F, hipMemcpyHostToDevice));
-  if (objective == 1 || objective == 2) {   // engine.cpp: logit base margin for the logistic objectives only
-    const double b = std::min(1 - 1e-7, std::max(1e-7, P[11]));
-    base = std::log(b / (1 - b));
-  }
-  {
-    std::vector<float> m((size_t)nfold * n * K, (float)base);
+    HC(ws.alloc_pinned(h_up, keys_bytes + sizeof(int) * K * order_elems));
+    HC(ws.alloc_pinned(h_met, sizeof(double) * met_elems));
+    HC(hipMemcpy(d_y, y_h, sizeof(float) * n, hipMemcpyHostToDevice));
+    HC(hipMemcpy(d_fold, fold_h, sizeof(int) * n, hipMemcpyHostToDevice));
+    HC(hipMemcpy(d_nb, nbins_h, sizeof(int) * F, hipMemcpyHostToDevice));
+    std::vector<float> m((size_t)nfold * n * K, (float)base_margin(objective, p.base_score));
     HC(hipMemcpy(d_margin, m.data(), sizeof(float) * m.size(), hipMemcpyHostToDevice));
+    return 0;
   }
 
-  for (int round = 0; round < num_boost_round; ++round) {
-    // ---- host: every tree's random draws (engine.cpp round_fold / build_tree streams)
+  // Every tree's random draws of the round, which do not depend on the data (cv_protocol.h draw_tree: the CPU
+  // engine's streams), into the pinned block, then one asynchronous copy each for the keys and the orders.
+  int draw_round(int round) {
     u64* h_keys = reinterpret_cast<u64*>(h_up);
-    int* h_order = reinterpret_cast<int*>(reinterpret_cast<char*>(h_up) + keys_bytes);
+    int* h_order = reinterpret_cast<int*>(h_up + keys_bytes);
     std::memset(h_order, 0, sizeof(int) * K * order_elems);
     for (int k = 0; k < nfold; ++k) {
-      const uint64_t fold_round = smix(seed ^ smix((uint64_t)k * 1000003ull + (uint64_t)round * 7919ull + 17));
+      const uint64_t fold_round = fold_round_seed(seed, k, round);
       for (int c = 0; c < K; ++c) {
-        uint64_t rs = c == 0 ? fold_round : smix(fold_round ^ smix((uint64_t)c * 0x51ED27ull + 3));
-        auto next = [&]() { rs = smix(rs); return rs; };
-        h_keys[(size_t)c * nfold + k] = P[5] < 1.0 ? next() : 0ull;
-        std::vector<int> feats(F);
-        for (int f = 0; f < F; ++f) feats[f] = f;
-        if (P[6] < 1.0) {
-          const int kk = std::max(1, (int)std::floor(P[6] * F + 1e-9));
-          for (int i = 0; i < F; ++i) std::swap(feats[i], feats[i + (int)(next() % (uint64_t)(F - i))]);
-          feats.resize(kk);
-          std::sort(feats.begin(), feats.end());
-        }
-        const uint64_t level_key = P[7] < 1.0 ? next() : 0ull;
+        Rng rng(class_stream(fold_round, c));
+        const TreeDraws t = draw_tree(rng, p, F);
+        h_keys[(size_t)c * nfold + k] = t.row_key;
         for (int d = 0; d <= D; ++d) {
-          std::vector<int> lf = feats;
-          if (P[7] < 1.0 && lf.size() > 1) {
-            const int m = (int)lf.size();
-            const int kk = std::max(1, (int)std::floor(P[7] * m + 1e-9));
-            uint64_t ls = smix(level_key ^ smix((uint64_t)d + 1));
-            for (int i = 0; i < m; ++i) {
-              ls = smix(ls);
-              std::swap(lf[i], lf[i + (int)(ls % (uint64_t)(m - i))]);
-            }
-            lf.resize(kk);
-          }
+          const std::vector<int> lf = level_features(t.feats, t.level_key, d, p);
           int* o = h_order + (size_t)c * order_elems + ((size_t)k * (D + 1) + d) * F;
-          for (int i = 0; i < (int)lf.size(); ++i) o[lf[i]] = i + 1;
+          for (int i = 0; i < (int)lf.size(); ++i) o[lf[i]] = i + 1;      // 1 + scan position, 0 = not sampled
         }
       }
     }
     HC(hipMemcpyAsync(d_keys, h_keys, keys_bytes, hipMemcpyHostToDevice, 0));
     HC(hipMemcpyAsync(d_order, h_order, sizeof(int) * K * order_elems, hipMemcpyHostToDevice, 0));
-    // ---- device: one tree per class for every fold, levels decided on the device
-    for (int c = 0; c < K; ++c) {
-      if (sink && round < trace_rounds && (trace_mask & GT_KEYS))
-        HC(emit(round, c, -1, GT_KEYS, d_keys + (size_t)c * nfold, sizeof(u64) * nfold));
-      if (sink && round < trace_rounds && (trace_mask & GT_ORDER))
-        HC(emit(round, c, -1, GT_ORDER, d_order + (size_t)c * order_elems, sizeof(int) * order_elems));
-      if (sink && round < trace_rounds && (trace_mask & GT_MARGIN))
-        HC(emit(round, c, -2, GT_MARGIN, d_margin, sizeof(float) * (size_t)nfold * n * K));
-      hipLaunchKernelGGL(grad_kernel, dim3(blocks, nfold), dim3(256), 0, 0, d_margin, d_y, d_gh, n, K, c, obj,
-                         (float)P[10]);
-      HC(hipMemsetAsync(d_mx, 0, sizeof(unsigned int) * 2 * nfold, 0));
-      hipLaunchKernelGGL(gh_max_kernel, dim3(std::min(blocks, 256), nfold), dim3(256), 0, 0, d_gh, n, d_mx);
-      if (sink && round < trace_rounds && (trace_mask & GT_GH))
-        HC(emit(round, c, -1, GT_GH, d_gh, sizeof(float2) * (size_t)nfold * n));
-      if (sink && round < trace_rounds && (trace_mask & GT_MX))
-        HC(emit(round, c, -1, GT_MX, d_mx, sizeof(unsigned int) * 2 * nfold));
-      HC(hipMemsetAsync(d_nroot, 0, sizeof(int) * nfold, 0));
-      hipLaunchKernelGGL(root_rows_kernel, dim3(std::max(1, std::min(1024, (n + 256 * RR_PER - 1) / (256 * RR_PER))), nfold),
-                         dim3(256), 0, 0, d_fold, n, d_keys + (size_t)c * nfold,
-                         P[5], d_rows[0], d_nroot);
-      hipLaunchKernelGGL(level0_kernel, dim3(nfold), dim3(64), 0, 0, geo, d_nroot, d_lvl[0], d_chunks, d_reds,
-                         d_counts);
-      if (sink && round < trace_rounds && (trace_mask & GT_ROOT))
-        HC(emit(round, c, -1, GT_ROOT, d_nroot, sizeof(int) * nfold, d_rows[0], sizeof(int) * (size_t)nfold * n));
-      const int* order_c = d_order + (size_t)c * order_elems;
-      for (int d = 0; d <= D; ++d) {
-        const int L = 1 << d;
-        LNode* cur = d_lvl[d & 1];
-        LNode* nxt = d_lvl[(d + 1) & 1];
-        i64* hcur = d_hist[d & 1];
-        if (d < D || d == 0) {
-          if (hconst)
-            hipLaunchKernelGGL(hist_kernel<true>, dim3(geo.maxch, nfb, nfold), dim3(HB_T), 0, 0, geo, d_bins,
-                               d_rows[d & 1], d_gh, d_chunks, d_counts, hcur, d_part, d_mx);
-          else
-            hipLaunchKernelGGL(hist_kernel<false>, dim3(geo.maxch, nfb, nfold), dim3(HB_T), 0, 0, geo, d_bins,
-                               d_rows[d & 1], d_gh, d_chunks, d_counts, hcur, d_part, d_mx);
-          // a reduced node has more than rch rows: at most n / (rch + 1) of them per fold
-          hipLaunchKernelGGL(reduce_kernel, dim3(std::max(1, n / (geo.rch + 1)), rlen, nfold), dim3(256), 0, 0, geo,
-                             d_part, hcur, d_reds, d_counts);
-          // siblings = parent - built child, materialised only where a later level subtracts from them
-          // (the last histogram level's split reads them as the difference)
-          if (d == 0)
-            hipLaunchKernelGGL(root_totals_kernel, dim3(nfold), dim3(64), 0, 0, geo, hcur, cur);
-          else if (d + 1 < D)
-            hipLaunchKernelGGL(subtract_kernel, dim3(L, ylen, nfold), dim3(256), 0, 0, geo, cur, d_hist[(d - 1) & 1],
-                               hcur);
-          if (sink && round < trace_rounds && (trace_mask & GT_HIST))
-            HC(emit(round, c, d, GT_HIST, hcur, sizeof(i64) * (size_t)nfold * geo.Lh * per_node));
-        }
-        if (sink && round < trace_rounds && (trace_mask & GT_LNODES))
-          HC(emit(round, c, d, GT_LNODES, cur, sizeof(LNode) * (size_t)nfold * geo.Lmax));
-        if (sink && round < trace_rounds && (trace_mask & GT_CHUNKS))
-          HC(emit(round, c, d, GT_CHUNKS, d_chunks, sizeof(Chunk) * (size_t)nfold * geo.maxch));
-        if (sink && round < trace_rounds && (trace_mask & GT_REDS))
-          HC(emit(round, c, d, GT_REDS, d_reds, sizeof(Red) * (size_t)nfold * geo.maxch));
-        if (sink && round < trace_rounds && (trace_mask & GT_COUNTS))
-          HC(emit(round, c, d, GT_COUNTS, d_counts, sizeof(int) * 2 * nfold));
-        if (d < D) {
-          hipLaunchKernelGGL(split_kernel, dim3(F, L, nfold), dim3(64), 0, 0, geo, d, hcur,
-                             (d > 0 && d + 1 == D) ? d_hist[(d - 1) & 1] : nullptr, d_nb, order_c, cur, d_mx, d_cand,
-                             dp);
-          if (sink && round < trace_rounds && (trace_mask & GT_CAND))
-            HC(emit(round, c, d, GT_CAND, d_cand, sizeof(SplitOut) * (size_t)nfold * geo.Lh * F));
-          hipLaunchKernelGGL(best_kernel, dim3(L, nfold), dim3(256), 0, 0, geo, d_cand, d_best);
-          if (sink && round < trace_rounds && (trace_mask & GT_BEST))
-            HC(emit(round, c, d, GT_BEST, d_best, sizeof(NodeBest) * (size_t)nfold * geo.Lh));
-        }
-        hipLaunchKernelGGL(plan_split_kernel, dim3(nfold), dim3(256), 0, 0, geo, d, cur, d_best, d_mx, d_tree, d_leaf,
-                           d_split, d_cur, nxt, dp);
-        if (sink && round < trace_rounds && (trace_mask & GT_SPLITV))
-          HC(emit(round, c, d, GT_SPLITV, d_split, sizeof(int2) * (size_t)nfold * geo.Lmax));
-        if (d < D) {
-          hipLaunchKernelGGL(partition_kernel, dim3(pblocks, nfold), dim3(256), 0, 0, geo, d, g_binsT, d_nroot, cur,
-                             d_split, d_rows[d & 1], d_rows[(d + 1) & 1], d_cur);
-          if (sink && round < trace_rounds && (trace_mask & GT_ROWS))
-            HC(emit(round, c, d, GT_ROWS, d_rows[(d + 1) & 1], sizeof(int) * (size_t)nfold * n));
-          hipLaunchKernelGGL(plan_next_kernel, dim3(nfold), dim3(256), 0, 0, geo, d, cur, d_split, d_cur, nxt,
-                             d_chunks, d_reds, d_counts);
-          if (sink && round < trace_rounds && (trace_mask & GT_NXT))
-            HC(emit(round, c, d, GT_NXT, nxt, sizeof(LNode) * (size_t)nfold * geo.Lmax));
-        }
+    return 0;
+  }
+
+  // One tree (class c) of every fold: gradients, root rows, the level loop decided on the device, predict.
+  int grow_tree(int round, int c) {
+    HC(tr.emit(round, c, -1, GT_KEYS, d_keys + (size_t)c * nfold, sizeof(u64) * nfold));
+    HC(tr.emit(round, c, -1, GT_ORDER, d_order + (size_t)c * order_elems, sizeof(int) * order_elems));
+    HC(tr.emit(round, c, -2, GT_MARGIN, d_margin, sizeof(float) * (size_t)nfold * n * K));
+    hipLaunchKernelGGL(grad_kernel, dim3(blocks, nfold), dim3(256), 0, 0, d_margin, d_y, d_gh, n, K, c, obj,
+                       (float)p.scale_pos_weight);
+    HC(hipMemsetAsync(d_mx, 0, sizeof(unsigned int) * 2 * nfold, 0));
+    hipLaunchKernelGGL(gh_max_kernel, dim3(std::min(blocks, 256), nfold), dim3(256), 0, 0, d_gh, n, d_mx);
+    HC(tr.emit(round, c, -1, GT_GH, d_gh, sizeof(float2) * (size_t)nfold * n));
+    HC(tr.emit(round, c, -1, GT_MX, d_mx, sizeof(unsigned int) * 2 * nfold));
+    HC(hipMemsetAsync(d_nroot, 0, sizeof(int) * nfold, 0));
+    hipLaunchKernelGGL(root_rows_kernel, dim3(std::max(1, std::min(1024, (n + 256 * RR_PER - 1) / (256 * RR_PER))), nfold),
+                       dim3(256), 0, 0, d_fold, n, d_keys + (size_t)c * nfold, p.subsample, d_rows[0], d_nroot);
+    hipLaunchKernelGGL(level0_kernel, dim3(nfold), dim3(64), 0, 0, geo, d_nroot, d_lvl[0], d_chunks, d_reds,
+                       d_counts);
+    HC(tr.emit(round, c, -1, GT_ROOT, d_nroot, sizeof(int) * nfold, d_rows[0], sizeof(int) * (size_t)nfold * n));
+    const int* order_c = d_order + (size_t)c * order_elems;
+    for (int d = 0; d <= D; ++d) {
+      const int L = 1 << d;
+      LNode* cur = d_lvl[d & 1];
+      LNode* nxt = d_lvl[(d + 1) & 1];
+      i64* hcur = d_hist[d & 1];
+      if (d < D || d == 0) {
+        hipLaunchKernelGGL(hconst ? hist_kernel<true> : hist_kernel<false>, dim3(geo.maxch, nfb, nfold), dim3(HB_T), 0,
+                           0, geo, d_bins, d_rows[d & 1], d_gh, d_chunks, d_counts, hcur, d_part, d_mx);
+        // a reduced node has more than rch rows: at most n / (rch + 1) of them per fold
+        hipLaunchKernelGGL(reduce_kernel, dim3(std::max(1, n / (geo.rch + 1)), rlen, nfold), dim3(256), 0, 0, geo,
+                           d_part, hcur, d_reds, d_counts);
+        // siblings = parent - built child, materialised only where a later level subtracts from them
+        // (the last histogram level's split reads them as the difference)
+        if (d == 0)
+          hipLaunchKernelGGL(root_totals_kernel, dim3(nfold), dim3(64), 0, 0, geo, hcur, cur);
+        else if (d + 1 < D)
+          hipLaunchKernelGGL(subtract_kernel, dim3(L, ylen, nfold), dim3(256), 0, 0, geo, cur, d_hist[(d - 1) & 1],
+                             hcur);
+        HC(tr.emit(round, c, d, GT_HIST, hcur, sizeof(i64) * (size_t)nfold * geo.Lh * per_node));
       }
-      if (sink && round < trace_rounds && (trace_mask & GT_TREE))
-        HC(emit(round, c, -1, GT_TREE, d_tree, sizeof(int2) * (size_t)nfold * tsz));
-      if (sink && round < trace_rounds && (trace_mask & GT_LEAF))
-        HC(emit(round, c, -1, GT_LEAF, d_leaf, sizeof(float) * (size_t)nfold * tsz));
-      hipLaunchKernelGGL(predict_kernel, dim3(std::min(blocks, 512), (nfold + pk - 1) / pk), dim3(256), pred_lds, 0,
-                         geo, d_bins, d_tree, d_leaf, d_margin, c, pk, pr_rows);
-      if (sink && round < trace_rounds && (trace_mask & GT_MARGIN))
-        HC(emit(round, c, -1, GT_MARGIN, d_margin, sizeof(float) * (size_t)nfold * n * K));
+      HC(tr.emit(round, c, d, GT_LNODES, cur, sizeof(LNode) * (size_t)nfold * geo.Lmax));
+      HC(tr.emit(round, c, d, GT_CHUNKS, d_chunks, sizeof(Chunk) * (size_t)nfold * geo.maxch));
+      HC(tr.emit(round, c, d, GT_REDS, d_reds, sizeof(Red) * (size_t)nfold * geo.maxch));
+      HC(tr.emit(round, c, d, GT_COUNTS, d_counts, sizeof(int) * 2 * nfold));
+      if (d < D) {
+        hipLaunchKernelGGL(split_kernel, dim3(F, L, nfold), dim3(64), 0, 0, geo, d, hcur,
+                           (d > 0 && d + 1 == D) ? d_hist[(d - 1) & 1] : nullptr, d_nb, order_c, cur, d_mx, d_cand,
+                           dp);
+        HC(tr.emit(round, c, d, GT_CAND, d_cand, sizeof(SplitOut) * (size_t)nfold * geo.Lh * F));
+        hipLaunchKernelGGL(best_kernel, dim3(L, nfold), dim3(256), 0, 0, geo, d_cand, d_best);
+        HC(tr.emit(round, c, d, GT_BEST, d_best, sizeof(NodeBest) * (size_t)nfold * geo.Lh));
+      }
+      hipLaunchKernelGGL(plan_split_kernel, dim3(nfold), dim3(256), 0, 0, geo, d, cur, d_best, d_mx, d_tree, d_leaf,
+                         d_split, d_cur, nxt, dp);
+      HC(tr.emit(round, c, d, GT_SPLITV, d_split, sizeof(int2) * (size_t)nfold * geo.Lmax));
+      if (d < D) {
+        hipLaunchKernelGGL(partition_kernel, dim3(pblocks, nfold), dim3(256), 0, 0, geo, d, d_binsT, d_nroot, cur,
+                           d_split, d_rows[d & 1], d_rows[(d + 1) & 1], d_cur);
+        HC(tr.emit(round, c, d, GT_ROWS, d_rows[(d + 1) & 1], sizeof(int) * (size_t)nfold * n));
+        hipLaunchKernelGGL(plan_next_kernel, dim3(nfold), dim3(256), 0, 0, geo, d, cur, d_split, d_cur, nxt,
+                           d_chunks, d_reds, d_counts);
+        HC(tr.emit(round, c, d, GT_NXT, nxt, sizeof(LNode) * (size_t)nfold * geo.Lmax));
+      }
     }
+    HC(tr.emit(round, c, -1, GT_TREE, d_tree, sizeof(int2) * (size_t)nfold * tsz));
+    HC(tr.emit(round, c, -1, GT_LEAF, d_leaf, sizeof(float) * (size_t)nfold * tsz));
+    hipLaunchKernelGGL(predict_kernel, dim3(std::min(blocks, 512), (nfold + pk - 1) / pk), dim3(256), pred_lds, 0,
+                       geo, d_bins, d_tree, d_leaf, d_margin, c, pk, pr_rows);
+    HC(tr.emit(round, c, -1, GT_MARGIN, d_margin, sizeof(float) * (size_t)nfold * n * K));
+    return 0;
+  }
+
+  // The round's metric launches and its blocking copies: early stopping needs the test metric.
+  int read_metrics(int round) {
     for (int mi = 0; mi < n_metrics; ++mi)
-      if (metrics[mi] != 4)
+      if (metrics[mi] != M_AUC)
         hipLaunchKernelGGL(metric_kernel, dim3(mblocks, nfold), dim3(256), 0, 0, geo, d_margin, d_y, d_fold,
                            metrics[mi], objective, d_met + (size_t)mi * nfold * mblocks * 4);
     if (want_auc) {
@@ -1297,87 +1217,102 @@ static int gbdt_cv_body(const uint8_t* bins_h, int Fs, const int* nbins_h, int n
                          d_asorted, aN, 2 * nfold, d_aacc);
     }
     HC(hipGetLastError());
-    // the round's blocking copies: early stopping needs the test metric
     HC(hipMemcpy(h_met, d_met, sizeof(double) * met_elems, hipMemcpyDeviceToHost));
     if (want_auc) HC(hipMemcpy(h_aacc.data(), d_aacc, sizeof(double) * 4 * nfold, hipMemcpyDeviceToHost));
-    if (sink && round < trace_rounds && (trace_mask & GT_MET))
-      sink(user, round, -1, -1, (int)GT_MET, h_met, (long long)(sizeof(double) * met_elems));
-    if (sink && round < trace_rounds && (trace_mask & GT_AUC) && want_auc)
-      sink(user, round, -1, -1, (int)GT_AUC, h_aacc.data(), (long long)(sizeof(double) * 4 * nfold));
-    double tem_last = 0;
+    tr.emit_host(round, GT_MET, h_met, sizeof(double) * met_elems);
+    if (want_auc) tr.emit_host(round, GT_AUC, h_aacc.data(), sizeof(double) * 4 * nfold);
+    return 0;
+  }
+
+  // The read-back -> the round's rows of out_hist; returns the mean test value of the last metric.
+  double fold_stats(int round, double* out_hist) const {
+    std::vector<double> trv(nfold), tev(nfold);
     for (int mi = 0; mi < n_metrics; ++mi) {
-      std::vector<double> trv(nfold), tev(nfold);
       for (int k = 0; k < nfold; ++k) {
-        if (metrics[mi] == 4) {         // engine.cpp auc_score: (R+ - n+(n+ + 1)/2) / (n+ n-), 0.5 if one class
-          auto auc = [](double r, double np, double nn) {
-            return (np == 0 || nn <= 0) ? 0.5 : (r - np * (np + 1) / 2) / (np * nn);
-          };
+        if (metrics[mi] == M_AUC) {
           const double* a = &h_aacc[4 * (size_t)k];
-          trv[k] = auc(a[0], a[1], (double)n - ntest[k] - a[1]);
-          tev[k] = auc(a[2], a[3], ntest[k] - a[3]);
+          trv[k] = auc_from_rank_sum(a[0], a[1], (double)n - ntest[k] - a[1]);
+          tev[k] = auc_from_rank_sum(a[2], a[3], ntest[k] - a[3]);
           continue;
         }
         double met[4] = {0, 0, 0, 0};
         const double* pm = h_met + ((size_t)mi * nfold + k) * mblocks * 4;
         for (int b = 0; b < mblocks; ++b)
           for (int q = 0; q < 4; ++q) met[q] += pm[(size_t)b * 4 + q];
-        double tr = met[0] / std::max(1.0, met[1]), te = met[2] / std::max(1.0, met[3]);
-        if (metrics[mi] == 0) { tr = std::sqrt(tr); te = std::sqrt(te); }
-        trv[k] = tr; tev[k] = te;
+        double tr_k = met[0] / std::max(1.0, met[1]), te_k = met[2] / std::max(1.0, met[3]);
+        if (metrics[mi] == M_RMSE) { tr_k = std::sqrt(tr_k); te_k = std::sqrt(te_k); }
+        trv[k] = tr_k; tev[k] = te_k;
       }
-      double trm = 0, tem = 0, trs = 0, tes = 0;
-      for (int k = 0; k < nfold; ++k) { trm += trv[k]; tem += tev[k]; }
-      trm /= nfold; tem /= nfold;
-      for (int k = 0; k < nfold; ++k) {
-        const double a = trv[k] - trm, b = tev[k] - tem;
-        trs += a * a; tes += b * b;
-      }
-      double* o = &out_hist[((size_t)round * n_metrics + mi) * 4];
-      o[0] = trm; o[1] = std::sqrt(trs / nfold); o[2] = tem; o[3] = std::sqrt(tes / nfold);
-      tem_last = tem;                  // early stopping on the last metric (engine.cpp)
+      write_fold_stats(trv.data(), tev.data(), nfold, &out_hist[((size_t)round * n_metrics + mi) * 4]);
     }
+    return out_hist[((size_t)round * n_metrics + (n_metrics - 1)) * 4 + 2];
+  }
+};
+
+}  // namespace
+
+extern "C" {
+
+// Same contract as gbdt_cv (csrc/gbdt/engine.cpp) for every objective (reg:linear/squarederror, reg:logistic,
+// binary:logistic/logitraw, multi:softmax/softprob: one tree per class) and every metric (rmse, mae, logloss,
+// error, auc, merror, mlogloss; early stopping on the last, auc maximised). auc needs nfold <= 32 (64 sort
+// segments). bins_h may be null when gbdt_quantize_hip already left the dataset's bins on the device under
+// cache_key (returns -7 if they were evicted). bins: ROW-major [n][Fs] uint8 (Fs >= F, Fs % 4 == 0).
+// cache_key != 0 keeps the device copy of the bins across calls for the same key (one dataset, many candidates).
+// With the stage trace: the first trace_rounds rounds hand the buffers selected by trace_mask (GT_* bits) to
+// sink. Same computation and return value with and without.
+int gbdt_cv_hip_trace(const uint8_t* bins_h, int Fs, const int* nbins_h, int n, int F, const float* y_h,
+                      const int* fold_h, int nfold, const double* P, int objective, int num_class,
+                      const int* metrics, int n_metrics, int num_boost_round, int early_stopping_rounds,
+                      unsigned long long seed, long long cache_key, double* out_hist, int trace_rounds,
+                      unsigned trace_mask, gbdt_trace_fn sink, void* user) {
+  if (objective < OBJ_SQUARED || objective > OBJ_MULTI_SOFTPROB || n_metrics < 1 || Fs % 4 || Fs < F || n <= 0 ||
+      nfold <= 0 || F <= 0)
+    return -1;
+  bool want_auc = false;
+  for (int mi = 0; mi < n_metrics; ++mi) {
+    if (metrics[mi] < M_RMSE || metrics[mi] > M_MLOGLOSS) return -1;
+    want_auc = want_auc || metrics[mi] == M_AUC;
+  }
+  if (want_auc && nfold > 32) return -1;
+  std::lock_guard<std::mutex> lock(gbdt_cache::mu);   // one GBDT call at a time per process (bins cache)
+  static const bool timing = std::getenv("GENTUN_GBDT_TIMING") != nullptr;
+  static const int progress = std::getenv("GENTUN_GBDT_PROGRESS") ? std::atoi(std::getenv("GENTUN_GBDT_PROGRESS")) : 0;
+  const auto t_start = std::chrono::steady_clock::now();
+  auto seconds = [&]() { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count(); };
+  CvRun r;
+  std::memcpy(&r.p, P, sizeof(Params));
+  r.objective = objective; r.metrics = metrics; r.n_metrics = n_metrics; r.seed = seed; r.want_auc = want_auc;
+  r.tr = Tracer{sink, user, trace_rounds, trace_mask};
+  r.shape(n, F, Fs, nfold, num_class, fold_h);
+  if (int rc = ensure_bins(bins_h, n, Fs, cache_key)) return rc;
+  r.d_bins = gbdt_cache::bins; r.d_binsT = gbdt_cache::binsT.bins;
+  if (int rc = r.allocate(y_h, fold_h, nbins_h)) return rc;
+  EarlyStop stop(metrics[n_metrics - 1], early_stopping_rounds);      // the last metric decides
+  int rounds_done = 0;
+  for (int round = 0; round < num_boost_round; ++round) {
+    if (int rc = r.draw_round(round)) return rc;
+    for (int c = 0; c < r.K; ++c)
+      if (int rc = r.grow_tree(round, c)) return rc;
+    if (int rc = r.read_metrics(round)) return rc;
+    const double tem_last = r.fold_stats(round, out_hist);
     rounds_done = round + 1;
     if (progress > 0 && rounds_done % progress == 0)
-      std::fprintf(stderr, "[gbdt_hip] round %d  test metric %.6g  %.2f s\n", rounds_done, tem_last,
-                   std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count());
-    if (lower_better ? tem_last < best_score : tem_last > best_score) { best_score = tem_last; best_round = round; }
-    if (early_stopping_rounds > 0 && round - best_round >= early_stopping_rounds) break;
+      std::fprintf(stderr, "[gbdt_hip] round %d  test metric %.6g  %.2f s\n", rounds_done, tem_last, seconds());
+    if (stop.update(round, tem_last)) break;
   }
   if (timing)
     std::fprintf(stderr, "[gbdt_hip] %d rounds x %d folds in %.3f s (fold-batched device levels, depth %d)\n",
-                 rounds_done, nfold,
-                 std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count(), D);
-  rc = early_stopping_rounds > 0 ? best_round + 1 : rounds_done;
-done:
-  for (void* p : {(void*)d_y, (void*)d_fold, (void*)d_nb, (void*)d_rows[0], (void*)d_rows[1], (void*)d_margin,
-                  (void*)d_gh, (void*)d_hist[0], (void*)d_hist[1], (void*)d_part, (void*)d_lvl[0], (void*)d_lvl[1],
-                  (void*)d_chunks, (void*)d_reds, (void*)d_counts, (void*)d_nroot, (void*)d_cand, (void*)d_best,
-                  (void*)d_tree, (void*)d_leaf, (void*)d_split, (void*)d_cur, (void*)d_mx, (void*)d_keys,
-                  (void*)d_order, (void*)d_met, (void*)d_akeys, (void*)d_asorted, (void*)d_atmp, (void*)d_aacc})
-    if (p) (void)hipFree(p);
-  if (h_up) (void)hipHostFree(h_up);
-  if (h_met) (void)hipHostFree(h_met);
-  return rc;
+                 rounds_done, nfold, seconds(), r.D);
+  return stop.kept_rows(rounds_done);
 }
 
 int gbdt_cv_hip(const uint8_t* bins_h, int Fs, const int* nbins_h, int n, int F, const float* y_h,
                 const int* fold_h, int nfold, const double* P, int objective, int num_class, const int* metrics,
                 int n_metrics, int num_boost_round, int early_stopping_rounds, unsigned long long seed,
                 long long cache_key, double* out_hist) {
-  return gbdt_cv_body(bins_h, Fs, nbins_h, n, F, y_h, fold_h, nfold, P, objective, num_class, metrics, n_metrics,
-                      num_boost_round, early_stopping_rounds, seed, cache_key, out_hist, 0, 0u, nullptr, nullptr);
-}
-
-// gbdt_cv_hip with the stage trace: the first trace_rounds rounds hand the buffers selected by trace_mask
-// (GT_* bits) to sink. Same computation and return value.
-int gbdt_cv_hip_trace(const uint8_t* bins_h, int Fs, const int* nbins_h, int n, int F, const float* y_h,
-                      const int* fold_h, int nfold, const double* P, int objective, int num_class,
-                      const int* metrics, int n_metrics, int num_boost_round, int early_stopping_rounds,
-                      unsigned long long seed, long long cache_key, double* out_hist, int trace_rounds,
-                      unsigned trace_mask, gbdt_trace_fn sink, void* user) {
-  return gbdt_cv_body(bins_h, Fs, nbins_h, n, F, y_h, fold_h, nfold, P, objective, num_class, metrics, n_metrics,
-                      num_boost_round, early_stopping_rounds, seed, cache_key, out_hist, trace_rounds, trace_mask,
-                      sink, user);
+  return gbdt_cv_hip_trace(bins_h, Fs, nbins_h, n, F, y_h, fold_h, nfold, P, objective, num_class, metrics, n_metrics,
+                           num_boost_round, early_stopping_rounds, seed, cache_key, out_hist, 0, 0u, nullptr, nullptr);
 }
 
 // struct sizes and constants the trace's reader needs: sizeof LNode, Chunk, Red, SplitOut, NodeBest; GB_R,

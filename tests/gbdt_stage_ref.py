@@ -21,7 +21,7 @@ def pdict(parr):
     return dict(zip(P_NAMES, (float(v) for v in parr)))
 
 
-# ---- random streams (engine.cpp splitmix / Rng / row_uniform / round_fold / build_tree) --------------------
+# ---- random streams (cv_protocol.h splitmix / Rng / row_uniform / draw_tree / level_features) ---------------
 
 def smix(x):
     x = (x + 0x9E3779B97F4A7C15) & M64
@@ -39,14 +39,14 @@ def _smix_u64(x):
 
 
 def row_uniform(key, rows):
-    """engine.cpp row_uniform for an array of row indices (uint64 arithmetic wraps like the C++)."""
+    """cv_protocol.h row_uniform for an array of row indices (uint64 arithmetic wraps like the C++)."""
     x = _smix_u64(np.uint64(key) ^ _smix_u64(np.asarray(rows).astype(np.uint64)))
     return (x >> np.uint64(11)).astype(np.float64) * (1.0 / 9007199254740992.0)
 
 
 def tree_draws(seed, k, rnd, c, F, D, p):
     """The draws of one tree (fold k, round, class c): the row-subsample key (0 without subsampling) and
-    every level's feature scan order (lists of feature indices), as engine.cpp round_fold / build_tree."""
+    every level's feature scan order (lists of feature indices), as cv_protocol.h draw_tree / level_features."""
     fold_round = smix((seed & M64) ^ smix((k * 1000003 + rnd * 7919 + 17) & M64))
     state = [fold_round if c == 0 else smix(fold_round ^ smix((c * 0x51ED27 + 3) & M64))]
 

@@ -193,3 +193,34 @@ def test_hip_outlier_gradients_match_cpu():
         a, b = np.array(cpu[k]), np.array(gpu[k])
         assert len(a) == len(b)
         assert np.max(np.abs(a - b) / a) < tol, (k, a[-5:], b[-5:])
+
+
+def test_hip_argument_errors_leave_engine_usable():
+    """The engine's early returns (-1 for no metric or an unknown objective, -7 for bins that are neither
+    passed nor cached) hold no buffer and leave the bins cache alone: the same run before and after them
+    gives bit-equal histories."""
+    import ctypes
+    from gentun_amd.models import gbdt_hip
+    x, y = make_regression(n=600, f=6, seed=2)
+    p = {'objective': 'reg:linear', 'max_depth': 3}
+    h0 = gbdt.cv(p, x, y, num_boost_round=2, nfold=3, seed=0, device="cuda:0")
+    xf = np.ascontiguousarray(x, dtype=np.float32)
+    yf = np.ascontiguousarray(y, dtype=np.float32)
+    fold_of = np.ascontiguousarray(np.arange(600) % 3, dtype=np.int32)
+    parr = np.array([gbdt.DEFAULTS[k] for k in gbdt.PARAM_ORDER], np.float64)
+    parr[2] = 3
+    marr = np.array([gbdt.METRICS['rmse']], np.int32)
+    hist = np.zeros((2, 1, 4), np.float64)
+    nb, key, fs = gbdt_hip.quantize_device(xf)
+
+    def raw(obj, n_metrics, cache_key):
+        return gbdt_hip._fn()(None, fs, nb.ctypes.data, 600, 6, yf.ctypes.data, fold_of.ctypes.data, 3,
+                              parr.ctypes.data, obj, 0, marr.ctypes.data, n_metrics, 2, 0, ctypes.c_ulonglong(0),
+                              cache_key, hist.ctypes.data)
+
+    assert raw(0, 0, key) == -1
+    assert raw(9, 1, key) == -1
+    assert raw(0, 1, key + 1000003) == -7
+    assert not hist.any()
+    assert raw(0, 1, key) == 2 and np.isfinite(hist).all() and hist[:, 0, 2].min() > 0
+    assert gbdt.cv(p, x, y, num_boost_round=2, nfold=3, seed=0, device="cuda:0") == h0
