@@ -75,6 +75,9 @@ struct ConvArgs {
   // 1: `w` holds FRAGMENT-MAJOR planes [planes][Q][NT][NKS][64][8] of the shape-specialised fp32 kernels
   // (gt_conv_wfrag, conv_fast_impl.h): each MFMA A fragment one contiguous KB in lane order
   int wfrag;
+  // 1: run the stage-2 3x3 fp32 8-row tile with two-pass patch staging (conv_fast_impl.h TWO) where the
+  // selection has that variant (gt_conv_fast_twopass); ignored by every other kernel. Same results.
+  int twopass;
 };
 
 __device__ __forceinline__ GroupRec group_rec(const GroupRec* gtab, int y, int n_in, int n_out, int acc,

@@ -78,8 +78,12 @@ static const std::vector<ConvRow>& conv_rows() {
     {8, 2, {tile<5, 5, 3, 16, 4, 4, 7, 4, 1>(IF_TH), ct1<5, 5, 3, 16, 2, 4, 7, 4>(IF_TH), ct1<5, 5, 3, 16, 8, 4, 7, 4, 0>()}},
     // s2 nodes / output conv, and their dgrad (50 -> 50): one co tile per wave, all 8 pixel groups (170 VGPRs
     // at 2 waves/SIMD): half the weight-fragment loads per MFMA of the 2 co x 4 group split, -1 % per
-    // population step at 25 and 80 groups (r5/conv_s2n_ct1_ab_r5.txt; the enforced-pipeline build spills here)
-    {8, 2, {tile<3, 3, 7, 16, 4, 4, 7, 4, 1>(IF_TH), ct1<3, 3, 7, 16, 2, 4, 7, 4>(IF_TH), ct1<3, 3, 7, 16, 8, 4, 7, 4, 0>()}},
+    // population step at 25 and 80 groups (r5/conv_s2n_ct1_ab_r5.txt; the enforced-pipeline build spills here).
+    // Launches that set ConvArgs::twopass run the 8-row tile with two-pass patch staging (35 KB of LDS instead
+    // of 70, 161 VGPRs: 3 workgroups per CU instead of 2; bit-identical, profiles/r7/conv_s2_twopass_r7.txt);
+    // the 4- and 2-row small-launch tiles are the same for either setting
+    {8, 2, {tile<3, 3, 7, 16, 4, 4, 7, 4, 1>(IF_TH), ct1<3, 3, 7, 16, 2, 4, 7, 4>(IF_TH),
+            ct1<3, 3, 7, 16, 8, 4, 7, 4, 0, 1>(IF_TWO), ct1<3, 3, 7, 16, 8, 4, 7, 4, 0>()}},
     // s2 input conv dgrad (50 -> 20): one co tile per wave while s2in_ct1 is on, else the packed tile
     {8, 4, {ct1<5, 5, 7, 16, 4, 2, 3, 4>(IF_S2CT1 | IF_TH), ct1<5, 5, 7, 16, 8, 2, 3, 4>(IF_S2CT1),
             tile<5, 5, 7, 16, 8, 2, 3, 4, 1, 1>(IF_PK), tile<5, 5, 7, 16, 8, 2, 3, 4, 1>()}},
@@ -129,7 +133,8 @@ struct ConvChoice {
 
 static bool variant_ok(const ConvArgs* a, const ConvRow& r, const ConvVariant& v) {
   return (!(v.cond & IF_TH) || smallq_th(a, r.hmod, r.thmin) == v.k.TH) && (!(v.cond & IF_PK) || pk_ok(a, v.k.NT)) &&
-         (!(v.cond & IF_RE) || g_fast.regepi) && (!(v.cond & IF_S2CT1) || g_fast.s2in_ct1);
+         (!(v.cond & IF_RE) || g_fast.regepi) && (!(v.cond & IF_S2CT1) || g_fast.s2in_ct1) &&
+         (!(v.cond & IF_TWO) || a->twopass);
 }
 
 // the search-space rows, then the user-chosen ones: the first row and variant whose condition holds
@@ -207,6 +212,25 @@ extern "C" int gt_conv_fast_select(const ConvArgs* a, ConvSel* s) {
   return 1;
 }
 extern "C" size_t gt_sizeof_conv_sel() { return sizeof(ConvSel); }
+
+// 1 when gt_conv_fast would run these arguments on a two-pass staging kernel (ConvSel has no room for the
+// flag), 0 on another shape-specialised kernel, -1 for no match. The executor probes with twopass = 1.
+extern "C" int gt_conv_fast_twopass(const ConvArgs* a) {
+  ConvChoice c;
+  if (a->wino || (a->prec != 0 && a->prec != 1) || !select_conv(a, &c)) return -1;
+  return c.k->TWO;
+}
+
+// workgroups of the kernel gt_conv_fast would launch that fit one CU at its registers, LDS and block size
+// (hipOccupancyMaxActiveBlocksPerMultiprocessor; needs a GPU), or -1
+extern "C" int gt_conv_fast_occupancy(const ConvArgs* a) {
+  ConvChoice c;
+  int n = 0;
+  if (a->wino || (a->prec != 0 && a->prec != 1) || !select_conv(a, &c)) return -1;
+  lds_limit(c.k->fn, c.lds);
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, c.k->fn, (int)c.block, c.lds) != hipSuccess) return -1;
+  return n;
+}
 
 __global__ void __launch_bounds__(256) wgrad_reduce_kernel(WgradArgs a) {
   const GroupRec gr = group_rec(a.gtab, blockIdx.y, a.n_in, 0, 0, nullptr);

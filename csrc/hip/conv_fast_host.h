@@ -29,16 +29,17 @@ extern FastSwitches g_fast;   // cnn_conv_fast.hip
 struct ConvKernel {
   int KH, KW, NCBI, W, TH, NT, NCO, NWV, PREC, PK, RE, CTX, SCH;
   int lds_fwd, lds_bwd;   // FastCfg::lds of forward (epi_bf16) and other launches
+  int TWO;                // two-pass patch staging (conv_fast_impl.h)
   const void* fn;
 };
 
 template <int KH, int KW, int NCBI, int W, int TH, int NT, int NCO, int NWV, int PREC, int PK = 0, int RE = 0,
-          int CTX = 0, int SCH = 0>
+          int CTX = 0, int SCH = 0, int TWO = 0>
 static ConvKernel conv_kernel() {
   static_assert((NCO * 8 + 15) / 16 == NT, "NT co tiles of 16 cover the NCO chunks of 8 channels");
-  using Cfg = FastCfg<KH, KW, NCBI, W, TH, NT, NCO, PREC>;
-  return {KH, KW, NCBI, W, TH, NT, NCO, NWV, PREC, PK, RE, CTX, SCH, (int)Cfg::lds(true), (int)Cfg::lds(false),
-          reinterpret_cast<const void*>(&conv_fast_kernel<KH, KW, NCBI, W, TH, NT, NCO, NWV, PREC, PK, RE, CTX, SCH>)};
+  using Cfg = FastCfg<KH, KW, NCBI, W, TH, NT, NCO, PREC, TWO>;
+  return {KH, KW, NCBI, W, TH, NT, NCO, NWV, PREC, PK, RE, CTX, SCH, (int)Cfg::lds(true), (int)Cfg::lds(false), TWO,
+          reinterpret_cast<const void*>(&conv_fast_kernel<KH, KW, NCBI, W, TH, NT, NCO, NWV, PREC, PK, RE, CTX, SCH, TWO>)};
 }
 
 // conditions of a variant (all must hold)
@@ -47,6 +48,7 @@ enum : int {
   IF_PK = 2,     // the packed last co tile applies (pk_ok)
   IF_RE = 4,     // register-epilogue switch on
   IF_S2CT1 = 8,  // s2in_ct1 switch on
+  IF_TWO = 16,   // the launch asks for two-pass patch staging (ConvArgs::twopass)
 };
 
 struct ConvVariant {
@@ -67,9 +69,9 @@ static ConvVariants tile(int cond = 0) {
 }
 
 // one co tile per wave (CTX 1), fp32, register-direct epilogue
-template <int KH, int KW, int NCBI, int W, int TH, int NT, int NCO, int NWV, int SCH = 1>
+template <int KH, int KW, int NCBI, int W, int TH, int NT, int NCO, int NWV, int SCH = 1, int TWO = 0>
 static ConvVariants ct1(int cond = 0) {
-  return {{cond, conv_kernel<KH, KW, NCBI, W, TH, NT, NCO, NWV, 1, 0, 1, 1, SCH>()}};
+  return {{cond, conv_kernel<KH, KW, NCBI, W, TH, NT, NCO, NWV, 1, 0, 1, 1, SCH, TWO>()}};
 }
 
 // One geometry (KH, KW, Cinp / 8, W, Coutp / 8, prec: those of its kernels) with H % hmod == 0. The first

@@ -62,9 +62,20 @@ struct S2Parts {
 // LDS bytes of one launch: the patch (NPL bf16 planes) or the output tile
 // (fp32, or bf16 for prec-0 forward launches -- measured 7-9 % faster: more
 // workgroups per CU), whichever is larger
-template <int KH, int KW, int NCBI, int W, int TH, int NT, int NCO, int PREC>
+// TWO (two-pass staging, S2Parts shapes only): the patch buffer holds one PART of the chunks at a time -- chunks
+// 0-3 for the k-steps of part 0, then chunks 4-6 staged into the same buffer for the k-steps of part 1 -- in the
+// pair layout over PART-LOCAL chunk indices (part 0: cb, part 1: cb - 4). Two pair-planes instead of four:
+// 35,040 B per workgroup instead of 70,080, so 4 workgroups fit a CU's LDS instead of 2. The reads of a k-step
+// keep their relative addresses (part 1 moves by two whole pair-planes), so the bank pattern is the pair
+// layout's: 576 read and 315 staging-write LDS cycles per tile in the model, as before
+// (tools/lds_patch_sim.py 3 3 7 16 8 two).
+template <int KH, int KW, int NCBI, int W, int TH, int NT, int NCO, int PREC, int TWO = 0>
 struct FastCfg {
+  static_assert(!TWO || S2Parts<KH, KW, NCBI, W, PREC>::on, "two-pass staging follows the part-major order");
   static constexpr int NPL = PREC ? GT_NPL_F32 : 1;
+  static constexpr int NC0 = TWO ? 4 : NCBI;          // chunks of part 0 (all of them without TWO)
+  static constexpr int NC1 = NCBI - NC0;              // chunks of part 1
+  static constexpr int NCL = NC0 > NC1 ? NC0 : NC1;   // most chunks in LDS at once
   static constexpr int PW = W + KW - 1;
   static constexpr int NP = (TH + KH - 1) * PW * NCBI;
   // LDS pixel stride of the patch in 16-byte chunks: odd (an even stride -- 8, 16, 32 chunks of
@@ -94,10 +105,12 @@ struct FastCfg {
   // only where the patch's LDS does not cost a workgroup per CU: the s1 3x3 tile (3 -> 2 workgroups per CU by
   // LDS) ran 7-14 % slower per launch in the pair layout, the stage-2 tiles 0.5-1.5 % faster, the population
   // step -0.8 % with this rule (profiles/r6/conv_patch_pair_r6.txt)
-  static constexpr bool PAIR = PREC == 1 && NCBI >= 2 && LDS_CU / LDS_PR >= LDS_CU / LDS_PM;
+  static constexpr bool PAIR = TWO || (PREC == 1 && NCBI >= 2 && LDS_CU / LDS_PR >= LDS_CU / LDS_PM);
   static constexpr int PXS = PAIR ? 2 : NCBP;       // LDS pixel stride (chunks)
-  static constexpr int NPP = PAIR ? ((NCBI + 1) / 2) * PP2 : NPIX * NCBP;
-  // LDS chunk offset of chunk cb within a pixel
+  static constexpr int NPP = PAIR ? ((NCL + 1) / 2) * PP2 : NPIX * NCBP;   // LDS plane stride (chunks)
+  // chunk cb -> its index among the chunks staged with it (TWO: within its part)
+  __host__ __device__ static constexpr int cloc(int cb) { return cb < NC0 ? cb : cb - NC0; }
+  // LDS chunk offset of (staged-together index) chunk cb within a pixel
   __host__ __device__ static constexpr int cbo(int cb) { return PAIR ? (cb >> 1) * PP2 + (cb & 1) : cb; }
   static size_t lds(bool fwd) {
     const size_t p = (size_t)NPP * 16 * NPL;
@@ -112,7 +125,11 @@ struct FastCfg {
 // tile; NWV = 8 waves per workgroup: half the pixels per wave (fewer
 // registers, 4 waves / SIMD) for the same 256-pixel tile. PREC 1 (fp32
 // tensors, six-term split MFMA): three operand planes per fragment, LDS-bound
-// at 2-3 workgroups per CU -> 2 waves / SIMD.
+// at 2-3 workgroups per CU -> 2 waves / SIMD. The stage-2 3x3 tile with two-pass
+// staging (TWO) is the exception: 35 KB of LDS (4 workgroups per CU by LDS) and
+// 161 registers without scratch (half a k-step's patch fragments at a time, a
+// 2-deep weight ring) -> 3 waves / SIMD, 3 resident workgroups per CU (measured,
+// profiles/r7/conv_s2_twopass_r7.txt; 4 waves / SIMD would need <= 128 registers).
 // Fused 2x2 max-pool of a forward tile (K4): TH x W output pixels in LDS
 // (ld(pixel, chunk, f) reads 8 channels) -> pooled chunks + the argmax mask
 // of pool_fwd_kernel (cnn_conv.hip: first strict maximum over (0,0), (0,1),
@@ -194,26 +211,24 @@ __device__ __forceinline__ void f32_epi_regs(const ConvArgs& a, const GroupRec& 
 // hipcc's own schedule sinks every prefetch next to its first use; that is hidden where two MFMA waves
 // share a SIMD (neutral on the 2-tile shapes, slower on stage 1) but not on the one-co-tile-per-wave
 // s2 input-conv data gradient (-13 %): r5/conv_f32_sched_pipe_ab_r5.txt
+// TWO (S2Parts shapes): two-pass patch staging. The part-major order reads chunks 0-3 in k-steps 0-8 and chunks
+// 4-6 in k-steps 9-15, so the workgroup stages part 0, runs its k-steps, then stages part 1 into the SAME
+// buffer (after a barrier) and runs the rest on the same accumulators: the same MFMAs in the same order
+// (bit-identical) from half the LDS -- 4 workgroups per CU by LDS instead of 2, built for 3 waves / SIMD, so a
+// workgroup's staging and epilogue overlap its neighbours' MFMAs (profiles/r7/conv_s2_twopass_r7.txt).
 template <int KH, int KW, int NCBI, int W, int TH, int NT, int NCO, int NWV = 4, int PREC = 0, int PK = 0, int RE = 0,
-          int CTX = 0, int SCH = 0>
+          int CTX = 0, int SCH = 0, int TWO = 0>
 __global__ void __launch_bounds__(NWV * 64)
-__attribute__((amdgpu_waves_per_eu(PREC ? 2 : (NWV == 8 ? 4 : (NT >= 4 ? (NCBI >= 7 ? 2 : 3) : 4)))))
+__attribute__((amdgpu_waves_per_eu(PREC ? (TWO ? 3 : 2) : (NWV == 8 ? 4 : (NT >= 4 ? (NCBI >= 7 ? 2 : 3) : 4)))))
 conv_fast_kernel(ConvArgs a) {
   typedef typename ActT<PREC>::T AT;
   constexpr int NPL = PREC ? GT_NPL_F32 : 1;
   constexpr int NTH = NWV * 64;                     // threads
   constexpr int PH = TH + KH - 1, PW = W + KW - 1;
-  constexpr int NP = PH * PW * NCBI;                // patch chunks (8 channels) per plane
-  using FCL = FastCfg<KH, KW, NCBI, W, TH, NT, NCO, PREC>;
+  using FCL = FastCfg<KH, KW, NCBI, W, TH, NT, NCO, PREC, TWO>;
   constexpr int NCBP = FCL::NCBP;                   // LDS chunks per patch pixel (pixel-major layout)
   constexpr int PXS = FCL::PXS;                     // LDS pixel stride (chunks)
   constexpr int NPP = FCL::NPP;                     // LDS plane stride (chunks)
-  // staged chunk i (pixel i / NCBI, chunk i % NCBI) -> its LDS slot
-  auto pslot = [&](int i) {
-    if constexpr (NCBP == NCBI && !FCL::PAIR) return i;
-    else return (i / NCBI) * PXS + FCL::cbo(i % NCBI);
-  };
-  constexpr int NPT = (NP + NTH - 1) / NTH;             // patch chunks per thread
   constexpr int NCH = KH * KW * NCBI;               // reduction chunks
   constexpr int NKS = (NCH + 3) / 4;                // k-steps (32 k each)
   // reduction order: entry e of the chunk list -> (kk = kh * KW + kw, cb); part-major for the
@@ -238,7 +253,8 @@ conv_fast_kernel(ConvArgs a) {
   // weight prefetch depth (k-steps; 3 planes each in prec 1). The S=(3,5) stage-2 tiles with one co tile per
   // wave hold 3 k-steps of weights (12 VGPRs each): -0.6 % per population step, 2 and 4 neither
   // (r5/conv_s2n_ct1_ab_r5.txt)
-  constexpr int PFM = PREC ? ((CTX == 1 && !SCH && NWV == 4 && NCBI <= 7) ? 3 : 2) : 4;
+  // (TWO: 2, its register budget is 168 for 3 waves / SIMD)
+  constexpr int PFM = PREC ? ((CTX == 1 && !SCH && NWV == 4 && NCBI <= 7 && !TWO) ? 3 : 2) : 4;
   constexpr int PF = NKS < PFM ? NKS : PFM;
   // fp32 enforced pipeline (SCH): the weights of k-step s+PF load into the ring slot k-step s-1 used, so
   // no load waits for an MFMA still reading its registers
@@ -248,7 +264,7 @@ conv_fast_kernel(ConvArgs a) {
   static_assert(!PK || (PREC == 1 && WC == 1), "packed last tile: fp32, every wave owns all co tiles");
   static_assert(W % 16 == 0 || 16 % W == 0, "pixel groups must tile image rows");
 
-  using FC = FastCfg<KH, KW, NCBI, W, TH, NT, NCO, PREC>;
+  using FC = FCL;
   constexpr int OROW = FC::OROW, OROWB = FC::OROWB;
   extern __shared__ __attribute__((aligned(16))) uint4 smem[];   // patch planes, then the output tile
   uint4* patch = smem;
@@ -329,121 +345,135 @@ conv_fast_kernel(ConvArgs a) {
   const int n_src = a.gather ? 1 : __builtin_popcount(gr.in_mask);
   const AT* src0 = a.gather ? static_cast<const AT*>(a.in[0]) + a.gather[((long)a.st->cur_step * a.G + g) * a.B + b] * img
                             : static_cast<const AT*>(a.in[__builtin_ctz(gr.in_mask | 0x100) & 7]) + gimg;
-  long poff[NPT];
-  bool pok[NPT];
+  // One staging pass: chunks CB0 .. CB0 + NC - 1 of every patch pixel (all NCBI of them; TWO: one part) into
+  // the LDS slots of their pass-local index, and the pass's share of the summed-input write-back.
+  auto stage = [&](auto cb0_, auto nc_) {
+    constexpr int CB0 = decltype(cb0_)::value, NC = decltype(nc_)::value;
+    constexpr int NP = PH * PW * NC;                  // patch chunks (8 channels) per plane
+    constexpr int NPT = (NP + NTH - 1) / NTH;         // patch chunks per thread
+    // staged chunk i (pixel i / NC, chunk CB0 + i % NC) -> its LDS slot
+    auto pslot = [&](int i) {
+      if constexpr (NCBP == NCBI && !FCL::PAIR) return i;
+      else return (i / NC) * PXS + FCL::cbo(i % NC);
+    };
+    long poff[NPT];
+    bool pok[NPT];
 #pragma unroll
-  for (int j = 0; j < NPT; ++j) {
-    const int i = tid + NTH * j;
-    const int cb = i % NCBI, pix = i / NCBI;
-    const int pr = pix / PW, pc = pix % PW;
-    const int hh = h0 - KH / 2 + pr, ww = pc - KW / 2;
-    pok[j] = i < NP && hh >= 0 && hh < a.H && ww >= 0 && ww < W;
-    poff[j] = ((long)hh * W + ww) * (NCBI * 8) + cb * 8;
-  }
-  if (a.dbg & 4) {
+    for (int j = 0; j < NPT; ++j) {
+      const int i = tid + NTH * j;
+      const int cb = CB0 + i % NC, pix = i / NC;
+      const int pr = pix / PW, pc = pix % PW;
+      const int hh = h0 - KH / 2 + pr, ww = pc - KW / 2;
+      pok[j] = i < NP && hh >= 0 && hh < a.H && ww >= 0 && ww < W;
+      poff[j] = ((long)hh * W + ww) * (NCBI * 8) + cb * 8;
+    }
+    if (a.dbg & 4) {
 #pragma unroll
-    for (int j = 0; j < NPT; ++j)
+      for (int j = 0; j < NPT; ++j)
 #pragma unroll
-      for (int p = 0; p < NPL; ++p)
-        if (tid + NTH * j < NP) patch[p * NPP + pslot(tid + NTH * j)] = make_uint4(0, 0, 0, 0);
-  } else if (!PREC && n_src == 1) {
-    uint4 v[NPT];
+        for (int p = 0; p < NPL; ++p)
+          if (tid + NTH * j < NP) patch[p * NPP + pslot(tid + NTH * j)] = make_uint4(0, 0, 0, 0);
+    } else if (!PREC && n_src == 1) {
+      uint4 v[NPT];
 #pragma unroll
-    for (int j = 0; j < NPT; ++j)
-      v[j] = *reinterpret_cast<const uint4*>(pok[j] ? (const void*)(src0 + poff[j]) : (const void*)gt_zero8);
+      for (int j = 0; j < NPT; ++j)
+        v[j] = *reinterpret_cast<const uint4*>(pok[j] ? (const void*)(src0 + poff[j]) : (const void*)gt_zero8);
 #pragma unroll
-    for (int j = 0; j < NPT; ++j)
-      if (tid + NTH * j < NP) patch[pslot(tid + NTH * j)] = v[j];
-  } else {
-    // chunks in batches of JB with the batch's loads in flight; N-ary DAG
-    // input summed in fp32 (prec 0: one rounding to bf16 at the end; prec 1:
-    // exact split of the fp32 sum into the three planes)
-    constexpr int JB = NPT < 5 ? NPT : 5;
+      for (int j = 0; j < NPT; ++j)
+        if (tid + NTH * j < NP) patch[pslot(tid + NTH * j)] = v[j];
+    } else {
+      // chunks in batches of JB with the batch's loads in flight; N-ary DAG
+      // input summed in fp32 (prec 0: one rounding to bf16 at the end; prec 1:
+      // exact split of the fp32 sum into the three planes)
+      constexpr int JB = NPT < 5 ? NPT : 5;
 #pragma unroll
-    for (int j0 = 0; j0 < NPT; j0 += JB) {
-      float acc8[JB][8];
-#pragma unroll
-      for (int j = 0; j < JB; ++j)
-#pragma unroll
-        for (int e = 0; e < 8; ++e) acc8[j][e] = 0.f;
-      if (n_src == 1) {
+      for (int j0 = 0; j0 < NPT; j0 += JB) {
+        float acc8[JB][8];
 #pragma unroll
         for (int j = 0; j < JB; ++j)
-          if (j0 + j < NPT && pok[j0 + j]) ld_chunk(src0 + poff[j0 + j], acc8[j]);
-      } else {
-        // DAG inputs two at a time: both inputs' chunk loads are in flight before either is
-        // summed (one input at a time waited a global round trip per input). Still summed in
-        // increasing slot order: bit-identical.
-        int m = gr.in_mask & 0xff;
-        while (m) {
-          const int k0 = __builtin_ctz(m);
-          m &= m - 1;
-          const bool two = m != 0;
-          const int k1 = two ? __builtin_ctz(m) : k0;
-          if (two) m &= m - 1;
-          const AT* s0 = static_cast<const AT*>(a.in[k0]) + gimg;
-          const AT* s1 = static_cast<const AT*>(a.in[k1]) + gimg;
-          float t0[JB][8], t1[JB][8];
 #pragma unroll
-          for (int j = 0; j < JB; ++j) {
-#pragma unroll
-            for (int e = 0; e < 8; ++e) t0[j][e] = t1[j][e] = 0.f;
-            if (j0 + j < NPT && pok[j0 + j]) {
-              ld_chunk(s0 + poff[j0 + j], t0[j]);
-              if (two) ld_chunk(s1 + poff[j0 + j], t1[j]);
-            }
-          }
+          for (int e = 0; e < 8; ++e) acc8[j][e] = 0.f;
+        if (n_src == 1) {
 #pragma unroll
           for (int j = 0; j < JB; ++j)
+            if (j0 + j < NPT && pok[j0 + j]) ld_chunk(src0 + poff[j0 + j], acc8[j]);
+        } else {
+          // DAG inputs two at a time: both inputs' chunk loads are in flight before either is
+          // summed (one input at a time waited a global round trip per input). Still summed in
+          // increasing slot order: bit-identical.
+          int m = gr.in_mask & 0xff;
+          while (m) {
+            const int k0 = __builtin_ctz(m);
+            m &= m - 1;
+            const bool two = m != 0;
+            const int k1 = two ? __builtin_ctz(m) : k0;
+            if (two) m &= m - 1;
+            const AT* s0 = static_cast<const AT*>(a.in[k0]) + gimg;
+            const AT* s1 = static_cast<const AT*>(a.in[k1]) + gimg;
+            float t0[JB][8], t1[JB][8];
 #pragma unroll
-            for (int e = 0; e < 8; ++e) acc8[j][e] += t0[j][e];
-          if (two) {
+            for (int j = 0; j < JB; ++j) {
+#pragma unroll
+              for (int e = 0; e < 8; ++e) t0[j][e] = t1[j][e] = 0.f;
+              if (j0 + j < NPT && pok[j0 + j]) {
+                ld_chunk(s0 + poff[j0 + j], t0[j]);
+                if (two) ld_chunk(s1 + poff[j0 + j], t1[j]);
+              }
+            }
 #pragma unroll
             for (int j = 0; j < JB; ++j)
 #pragma unroll
-              for (int e = 0; e < 8; ++e) acc8[j][e] += t1[j][e];
+              for (int e = 0; e < 8; ++e) acc8[j][e] += t0[j][e];
+            if (two) {
+#pragma unroll
+              for (int j = 0; j < JB; ++j)
+#pragma unroll
+                for (int e = 0; e < 8; ++e) acc8[j][e] += t1[j][e];
+            }
+          }
+        }
+#pragma unroll
+        for (int j = 0; j < JB; ++j) {
+          const int i = tid + NTH * (j0 + j);
+          if (j0 + j >= NPT || i >= NP) continue;
+          if (PREC) {
+            uint4 p0, p1, p2;
+            split8(acc8[j], p0, p1, p2);
+            patch[pslot(i)] = p0;
+            patch[NPP + pslot(i)] = p1;
+            patch[2 * NPP + pslot(i)] = p2;
+          } else {
+            patch[pslot(i)] = pack8(acc8[j]);
           }
         }
       }
-#pragma unroll
-      for (int j = 0; j < JB; ++j) {
-        const int i = tid + NTH * (j0 + j);
-        if (j0 + j >= NPT || i >= NP) continue;
+    }
+    if (a.xsum && n_src > 1) {
+      // the summed input of this band (interior of the patch) for the layer's wgrad
+      __syncthreads();
+      AT* xo = static_cast<AT*>(a.xsum) + ((long)g * a.B + b) * img + (long)h0 * W * NCBI * 8;
+      for (int i = tid; i < TH * W * NC; i += NTH) {
+        const int cl = i % NC, pix = i / NC;
+        const int r = pix / W, c = pix % W;
+        if (h0 + r >= a.H) continue;
+        const int pi = ((r + KH / 2) * PW + c + KW / 2) * PXS + FCL::cbo(cl);
+        const long o = NC == NCBI ? (long)i * 8 : ((long)pix * NCBI + CB0 + cl) * 8;
         if (PREC) {
-          uint4 p0, p1, p2;
-          split8(acc8[j], p0, p1, p2);
-          patch[pslot(i)] = p0;
-          patch[NPP + pslot(i)] = p1;
-          patch[2 * NPP + pslot(i)] = p2;
+          float f[8];
+          join8(patch[pi], patch[NPP + pi], patch[2 * NPP + pi], f);   // exact: the fp32 sum
+          st_chunk(xo + o, f);
         } else {
-          patch[pslot(i)] = pack8(acc8[j]);
+          *reinterpret_cast<uint4*>(xo + o) = patch[pi];
         }
       }
     }
-  }
-  if (a.xsum && n_src > 1) {
-    // the summed input of this band (interior of the patch) for the layer's wgrad
-    __syncthreads();
-    AT* xo = static_cast<AT*>(a.xsum) + ((long)g * a.B + b) * img + (long)h0 * W * NCBI * 8;
-    for (int i = tid; i < TH * W * NCBI; i += NTH) {
-      const int cb = i % NCBI, pix = i / NCBI;
-      const int r = pix / W, c = pix % W;
-      if (h0 + r >= a.H) continue;
-      const int pi = ((r + KH / 2) * PW + c + KW / 2) * PXS + FCL::cbo(cb);
-      if (PREC) {
-        float f[8];
-        join8(patch[pi], patch[NPP + pi], patch[2 * NPP + pi], f);   // exact: the fp32 sum
-        st_chunk(xo + (long)i * 8, f);
-      } else {
-        *reinterpret_cast<uint4*>(xo + (long)i * 8) = patch[pi];
-      }
-    }
-  }
-  // chunk c -> patch offset of its (kh, kw, cb) relative to the output pixel
+  };
+  stage(std::integral_constant<int, 0>(), std::integral_constant<int, FCL::NC0>());
+  // chunk c -> patch offset of its (kh, kw, cb) relative to the output pixel (TWO: cb within its part)
   for (int c = tid; c < NKS * 4; c += NTH) {
     int kk, cb;
     ent(c, kk, cb);
-    coff[c] = c < NCH ? ((kk / KW) * PW + (kk % KW)) * PXS + FCL::cbo(cb) : 0;
+    coff[c] = c < NCH ? ((kk / KW) * PW + (kk % KW)) * PXS + FCL::cbo(FCL::cloc(cb)) : 0;
   }
   // first PF k-steps of weights in flight before the barrier (after the patch
   // staging: its registers are dead by now -- lower peak register pressure)
@@ -479,20 +509,57 @@ conv_fast_kernel(ConvArgs a) {
     const int c = s * 4 + kq;
     int kk, cb;
     ent(c, kk, cb);
-    return c < NCH ? ((kk / KW) * PW + (kk % KW)) * PXS + FCL::cbo(cb) : 0;
+    return c < NCH ? ((kk / KW) * PW + (kk % KW)) * PXS + FCL::cbo(FCL::cloc(cb)) : 0;
   };
-  // the patch fragments of k-step s: the offset from the LDS table, or (pipelined loop) computed in
-  // registers so no table read drains lgkmcnt in the middle of the MFMA stream
-  auto load_b = [&](int s, uint4 (*dst)[NPL]) {
+  // the patch fragments of N pixel groups (from the wave's group h0 on) of k-step s: the offset from the LDS
+  // table, or (pipelined loop) computed in registers so no table read drains lgkmcnt in the middle of the
+  // MFMA stream
+  auto load_bn = [&](int s, int h0, auto n_, uint4 (*dst)[NPL]) {
     const uint4* pb = patch + lbase + gbase + (SCHED ? koff(s) : coff[s * 4 + kq]);
 #pragma unroll
-    for (int h = 0; h < PG; ++h) {
-      const int p = h * 16;                        // relative to the wave's first group
+    for (int h = 0; h < decltype(n_)::value; ++h) {
+      const int p = (h0 + h) * 16;                 // relative to the wave's first group
 #pragma unroll
       for (int q = 0; q < NPL; ++q) dst[h][q] = pb[q * NPP + ((p / W) * PW + (p % W)) * PXS];
     }
   };
-  if (!(a.dbg & 1)) {
+  auto load_b = [&](int s, uint4 (*dst)[NPL]) { load_bn(s, 0, std::integral_constant<int, PG>(), dst); };
+  // fp32: k-steps S0 .. S1 - 1 in batches of PGB pixel groups; the next batch's patch fragments are read
+  // while this batch's 6 x CT x PGB MFMAs run (the unpipelined loop waited for its LDS reads before every
+  // k-step). TWO reads half a k-step's groups at a time: 96 fragment registers less, for 3 waves / SIMD;
+  // every accumulator still sees its MFMAs in k-step order.
+  constexpr int NBB = TWO ? 2 : 1, PGB = PG / NBB;
+  static_assert(PG % NBB == 0, "fragment batches split the wave's pixel groups evenly");
+  auto ksteps = [&](auto s0_, auto s1_, uint4 (&bfr)[2][PGB][NPL]) {
+    constexpr int Q0 = decltype(s0_)::value * NBB, Q1 = decltype(s1_)::value * NBB;
+    constexpr std::integral_constant<int, PGB> n;
+    load_bn(Q0 / NBB, 0, n, bfr[Q0 & 1]);
+#pragma unroll
+    for (int q = Q0; q < Q1; ++q) {
+      const int s = q / NBB, hb = (q % NBB) * PGB;
+      if (q + 1 < Q1) load_bn((q + 1) / NBB, ((q + 1) % NBB) * PGB, n, bfr[(q + 1) & 1]);
+#pragma unroll
+      for (int t = 0; t < CT; ++t)
+#pragma unroll
+        for (int h = 0; h < PGB; ++h) acc[t][hb + h] = mma(t, areg[s % PF][t], bfr[q & 1][h], acc[t][hb + h]);
+      if (q % NBB == NBB - 1 && s + PF < NKS) load_a(s + PF, areg[s % PF]);
+    }
+  };
+  if constexpr (TWO != 0) {
+    // part 0's k-steps, then part 1 staged over it once every wave's patch reads have returned; the weight
+    // ring keeps streaming across the restaging. No part-1 load is issued before the barrier: the other
+    // workgroups of the CU hide that latency, not registers held through part 0's k loop.
+    static_assert(PARTS && PREC != 0 && !SCHED && NKS <= 64 && S2Parts<KH, KW, NCBI, W, PREC>::e0 % 4 == 0,
+                  "two-pass staging: part 0 ends on a k-step boundary of the part-major order");
+    constexpr int KS0 = S2Parts<KH, KW, NCBI, W, PREC>::e0 / 4;
+    uint4 bfr[2][PGB][NPL];
+    if (!(a.dbg & 1)) ksteps(std::integral_constant<int, 0>(), std::integral_constant<int, KS0>(), bfr);
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __syncthreads();
+    stage(std::integral_constant<int, FCL::NC0>(), std::integral_constant<int, FCL::NC1>());
+    __syncthreads();
+    if (!(a.dbg & 1)) ksteps(std::integral_constant<int, KS0>(), std::integral_constant<int, NKS>(), bfr);
+  } else if (!(a.dbg & 1)) {
     if constexpr (PREC != 0 && NKS > 64) {
       // long reductions (wide layers: 72-100 k-steps): a runtime loop over k-step PAIRS, so the
       // register sets stay compile-time indexed (a fully unrolled loop this long is not unrolled
@@ -538,19 +605,8 @@ conv_fast_kernel(ConvArgs a) {
         __builtin_amdgcn_sched_barrier(0);
       }
     } else if constexpr (PREC != 0) {
-      // fp32: the next k-step's patch fragments are read while this step's 6 x CT x PG
-      // MFMAs run (the unpipelined loop waited for its LDS reads before every k-step)
       uint4 bfr[2][PG][NPL];
-      load_b(0, bfr[0]);
-#pragma unroll
-      for (int s = 0; s < NKS; ++s) {
-        if (s + 1 < NKS) load_b(s + 1, bfr[(s + 1) & 1]);
-#pragma unroll
-        for (int t = 0; t < CT; ++t)
-#pragma unroll
-          for (int h = 0; h < PG; ++h) acc[t][h] = mma(t, areg[s % PF][t], bfr[s & 1][h], acc[t][h]);
-        if (s + PF < NKS) load_a(s + PF, areg[s % PF]);
-      }
+      ksteps(std::integral_constant<int, 0>(), std::integral_constant<int, NKS>(), bfr);
     } else {
       // bf16
 #pragma unroll

@@ -80,6 +80,12 @@ WINOGRAD = False
 # then skips the row-major bf16 planes of those layers. Module constant; tests flip it.
 WFRAG = True
 
+# forward and data-gradient launches of the stage-2 3x3 fp32 shape (16x16, 56 -> 56 padded channels) ask for the
+# 8-row tile with two-pass patch staging (ConvArgs::twopass: half the LDS per workgroup, 3 workgroups per CU
+# instead of 2; bit-identical, profiles/r7/conv_s2_twopass_r7.txt) wherever the selection has it
+# (gt_conv_fast_twopass). Module constant; tests flip it.
+TWOPASS = True
+
 # bytes of forward-only activation twins an evaluation may allocate for all groups of a job
 EVAL_TWIN_BUDGET = 1 << 30
 
@@ -370,11 +376,13 @@ class HipPopJob(FoldJob):
             L.part_b = torch.zeros((L.S, Q, L.coutp), dtype=torch.float32, device=dev)
         self.wino_tr = K.WinoTransform(wsegs, dev) if wsegs else None
         # fragment-major planes for every layer direction a shape-specialised kernel runs
+        # (not with the fast path switched off, gt_conv_set_fast(0): the generic kernels refuse these planes)
         fspecs = []
+        frag_on = WFRAG and K.fast_path_on(self.L)
         for L in self.layers:
             first = L.slots == ["input"]
             L.wfrag = L.wfragT = False
-            if not WFRAG or L.wino:
+            if not frag_on or L.wino:
                 continue
             nr = max(1, len(L.rows))
             if K._probe_conv(self.L, L.KH, L.KW, L.cinp, L.coutp, L.H, L.W, self.prec, nr, B, L.cout, True):
@@ -490,6 +498,13 @@ class HipPopJob(FoldJob):
         a.wps = w[0].numel()                 # weights are [planes][...]
         return a
 
+    def _set_twopass(self, a):
+        """ConvArgs::twopass of a finished launch: 1 where the fast path is on and the selection has a
+        two-pass staging kernel for these arguments."""
+        a.twopass = 1 if TWOPASS and K.fast_path_on(self.L) else 0
+        if a.twopass and self.L.gt_conv_fast_twopass(a) != 1:
+            a.twopass = 0
+
     def _bn_args(self, L, train, pools=()):
         """``pools``: groups whose pool source is this layer (fused BN -> ReLU -> 2x2 max-pool)."""
         a = K.BnArgs()
@@ -538,6 +553,7 @@ class HipPopJob(FoldJob):
             a.epi_bf16 = 1            # forward outputs never accumulate: bf16 output tile
             if cpools:
                 a.pool_y, a.pool_mask = self.act[st.pool].data_ptr(), st.pmask.data_ptr()
+            self._set_twopass(a)
             ops.append(("conv", a, L))
             if self.bn:
                 b = self._bn_args(L, 1, pools)
@@ -715,6 +731,7 @@ class HipPopJob(FoldJob):
                         a.pool_y, a.pool_mask = self.grad[st.inp].data_ptr(), st.pmask.data_ptr()
                         a.unpool_x1 = self.grad[self.sched.pool_x1(st)].data_ptr()
                         a.unpool_sel = st.sel.data_ptr()
+                    self._set_twopass(a)
                     return a
                 a = None
                 if fuse_bwd and len(L.slots) == 1 and L.slots[0] in pool_stage:
@@ -1052,6 +1069,7 @@ class HipPopJob(FoldJob):
                 b.pool_y = rp(b.pool_y or 0)
                 b.pool_mask = 0                      # fused pool: output only
                 b.B = EB
+                self._set_twopass(b)                 # the evaluation batch may select another tile
                 ops.append((kind, b, Lr))
             elif kind == "bn":
                 b = K.BnArgs.from_buffer_copy(a)

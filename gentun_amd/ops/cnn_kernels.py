@@ -37,7 +37,7 @@ class ConvArgs(C.Structure):
                 ("G", I), ("B", I), ("H", I), ("W", I), ("Cinp", I), ("Coutp", I), ("KH", I), ("KW", I),
                 ("TH", I), ("ngroups", I), ("xsum", P), ("dbg", I), ("epi_bf16", I), ("prec", I), ("wps", C.c_long),
                 ("cbb", I), ("pool_y", P), ("pool_mask", P), ("unpool_x1", P), ("unpool_sel", P),
-                ("cout_real", I), ("Hr", I), ("Wr", I), ("wino", I), ("wfrag", I)]
+                ("cout_real", I), ("Hr", I), ("Wr", I), ("wino", I), ("wfrag", I), ("twopass", I)]
 
 
 class WinoWSeg(C.Structure):
@@ -288,6 +288,10 @@ def lib():
         L.gt_conv_fast_probe_any.restype = I
         L.gt_conv_fast_select.argtypes = [C.POINTER(ConvArgs), C.POINTER(ConvSel)]
         L.gt_conv_fast_select.restype = I
+        L.gt_conv_fast_twopass.argtypes = [C.POINTER(ConvArgs)]
+        L.gt_conv_fast_twopass.restype = I
+        L.gt_conv_fast_occupancy.argtypes = [C.POINTER(ConvArgs)]
+        L.gt_conv_fast_occupancy.restype = I
         L.gt_wgrad_fast_select.argtypes = [C.POINTER(WgradArgs), C.POINTER(WgradSel)]
         L.gt_wgrad_fast_select.restype = I
         L.gt_sizeof_conv_sel.restype = C.c_size_t

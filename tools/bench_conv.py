@@ -4,6 +4,8 @@ diagnostic ``dbg`` switches (bit 0 skip MFMA, 1 skip stores, 2 skip loads)
 to split a kernel's time into its phases. HIP-graph replay, events.
 
 usage: DTYPE=fp32 G=80 python tools/bench_conv.py [reps]
+TWOPASS=1 sets ConvArgs::twopass on the forward / data-gradient launches (the stage-2 3x3 fp32 tile with
+two-pass patch staging); the library's defaults stay as they are.
 Prints one JSON line per (kernel, shape, dbg): us per call, useful TFLOP/s,
 ideal MFMA-bound us (2.5 PF bf16 / number of MFMA terms per product).
 """
@@ -23,6 +25,7 @@ prec, npl = K.PREC[DT], K.NPL[DT]
 adt = torch.float32 if prec else torch.bfloat16
 G, B = int(os.environ.get("G", "80")), 32
 DBGS = [int(d) for d in os.environ.get("DBGS", "0,1,2,4,7").split(",")]
+TWOPASS = int(os.environ.get("TWOPASS", "0"))
 dev = torch.device("cuda", 0)
 L = K.lib()
 L.gt_conv_set_regepi.argtypes = [__import__("ctypes").c_int]
@@ -94,7 +97,7 @@ for name, H, cin, cout, k, nin in shapes:
                 a.xsum = xsum.data_ptr() if nin > 1 else 0
                 a.G, a.B, a.H, a.W, a.Cinp, a.Coutp, a.KH, a.KW = G, B, H, W, cinp, coutp, k, k
                 a.TH, a.prec, a.dbg = K.conv_tile_rows(H, W), prec, dbg
-                a.cout_real = cout
+                a.cout_real, a.twopass = cout, TWOPASS
                 fn = lambda s: K.check(L.gt_conv_fwd(a, s), kind)      # noqa: E731
             elif kind == "conv_dgrad":
                 a = K.ConvArgs()
@@ -103,7 +106,7 @@ for name, H, cin, cout, k, nin in shapes:
                 a.w, a.bias, a.st, a.wps = wT.data_ptr(), 0, st.data_ptr(), wT[0].numel()
                 a.G, a.B, a.H, a.W, a.Cinp, a.Coutp, a.KH, a.KW = G, B, H, W, coutp, cinp, k, k
                 a.TH, a.prec, a.dbg = K.conv_tile_rows(H, W), prec, dbg
-                a.cout_real = cin
+                a.cout_real, a.twopass = cin, TWOPASS
                 fn = lambda s: K.check(L.gt_conv_fwd(a, s), kind)      # noqa: E731
             else:
                 npix = B * H * W
@@ -122,6 +125,7 @@ for name, H, cin, cout, k, nin in shapes:
                 a.cout_real = cout
                 fn = lambda s: K.check(L.gt_conv_wgrad(a, s), kind)    # noqa: E731
             us = timeit(fn)
-            print(json.dumps({"regepi": os.environ.get("REGEPI", "1"), "dtype": DT, "G": G, "kernel": kind, "shape": name, "dbg": dbg, "us": round(us, 1),
+            two = kind != "conv_wgrad" and a.twopass and L.gt_conv_fast_twopass(a) == 1
+            print(json.dumps({"regepi": os.environ.get("REGEPI", "1"), "twopass": int(two), "dtype": DT, "G": G, "kernel": kind, "shape": name, "dbg": dbg, "us": round(us, 1),
                               "tflops_useful": round(flops / us / 1e6, 1),
                               "mfma_floor_us": round(floor_us, 1), "mfma_eff": round(floor_us / us, 3)}), flush=True)

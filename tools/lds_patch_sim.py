@@ -4,12 +4,14 @@ tile) and every ds_write_b128 8-lane group of the staging, for the pixel-major l
 chunks) and the PAIR layout (chunk pairs side by side, pixel stride 2, pair-plane stride PP2).
 Lane groups / banking: /opt/skills/guides/MI355X_MICROARCH.md (LDS table).
 
-usage: python tools/lds_patch_sim.py KH KW NCBI W TH [parts]   (parts: the stage-2 part-major order)
+usage: python tools/lds_patch_sim.py KH KW NCBI W TH [parts|two]   (parts: the stage-2 part-major order;
+two: that order with two-pass staging -- chunks 0-3, then chunks 4-6 in the same two pair-planes)
 """
 import sys
 
 KH, KW, NCBI, W, TH = (int(v) for v in (sys.argv[1:6] if len(sys.argv) > 5 else (3, 3, 7, 16, 8)))
-PARTS = len(sys.argv) > 6 and sys.argv[6] == "parts" or len(sys.argv) <= 5
+TWO = len(sys.argv) > 6 and sys.argv[6] == "two"
+PARTS = TWO or len(sys.argv) > 6 and sys.argv[6] == "parts" or len(sys.argv) <= 5
 PH, PW = TH + KH - 1, W + KW - 1
 NPIX = PH * PW
 NCH = KH * KW * NCBI
@@ -51,15 +53,16 @@ def read_cycles(slot):
     return tot
 
 
-def write_cycles(slot):
-    NP, tot = NPIX * NCBI, 0
+def write_cycles(slot, cb0=0, nc=NCBI):
+    """staging pass of chunks cb0 .. cb0 + nc - 1 (all of them: the one-pass kernel)"""
+    NP, tot = NPIX * nc, 0
     for j in range((NP + 255) // 256):
         for w0 in range(0, 256, 8):
             cnt = {}
             for t in range(w0, w0 + 8):
                 i = t + 256 * j
                 if i < NP:
-                    c = slot(i // NCBI, i % NCBI) % 8
+                    c = slot(i // nc, cb0 + i % nc) % 8
                     cnt[c] = cnt.get(c, 0) + 1
             if cnt:
                 tot += max(cnt.values())
@@ -75,6 +78,13 @@ for r in range(8):
     PP2 = 2 * NPIX + (r - 2 * NPIX) % 8
     new = lambda pix, cb, PP2=PP2: (cb >> 1) * PP2 + pix * 2 + (cb & 1)
     print("  pair PP2={} (= {} mod 8): read {} write {}".format(PP2, PP2 % 8, read_cycles(new), write_cycles(new)))
+if TWO:
+    # two-pass staging: the pair layout over part-local chunks (part 0: cb, part 1: cb - 4), two pair-planes
+    for r in range(8):
+        PP2 = 2 * NPIX + (r - 2 * NPIX) % 8
+        two = lambda pix, cb, PP2=PP2: ((cb % 4) >> 1) * PP2 + pix * 2 + (cb & 1)
+        print("  two-pass PP2={} (= {} mod 8): read {} write {} + {}  ({} B of LDS, 3 planes)".format(
+            PP2, PP2 % 8, read_cycles(two), write_cycles(two, 0, 4), write_cycles(two, 4, NCBI - 4), 2 * PP2 * 48))
 # PAIR with the unpaired last chunk (odd NCBI) at pixel stride 1 in its own plane: the pixel-major LDS size
 if NCBI & 1 and NCBI > 1:
     for r in range(8):

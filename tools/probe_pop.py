@@ -2,7 +2,8 @@
 split into jobs of ``pop_batch`` on ``streams`` streams, 1 epoch each.
 
 usage: python tools/probe_pop.py [P] [pop_batch] [streams] [epochs] [samples]
-Env: WINO=0/1 (Winograd stage-2 3x3 layers), WFRAG=0/1 (fragment-major conv weights), SHAPE=28,28,1 (MNIST-shaped: the reference default, stored zero-padded to 32 x 32 unless PAD=0),
+Env: WINO=0/1 (Winograd stage-2 3x3 layers), WFRAG=0/1 (fragment-major conv weights), TWOPASS=0/1 (two-pass
+staging of the stage-2 3x3 fp32 conv), SHAPE=28,28,1 (MNIST-shaped: the reference default, stored zero-padded to 32 x 32 unless PAD=0),
 SPACE=deep, KERNELS=, BN=1, DTYPE=, RESET=, GRAPH=0, WARM=0.
 """
 import json
@@ -31,7 +32,10 @@ if os.environ.get("WINO") is not None:                # A/B: Winograd stage-2 3x
 if os.environ.get("WFRAG") is not None:               # A/B: fragment-major conv weight planes on (1) / off (0)
     from gentun_amd.models import cnn_hip as _ch
     _ch.WFRAG = os.environ["WFRAG"] != "0"
-if os.environ.get("BNVALUES"):                      # A/B: BatchNorm values per workgroup budget (cnn_kernels)
+if os.environ.get("TWOPASS") is not None:             # A/B: two-pass staging of the stage-2 3x3 fp32 conv on / off
+    from gentun_amd.models import cnn_hip as _ch2
+    _ch2.TWOPASS = os.environ["TWOPASS"] != "0"
+if os.environ.get("BNVALUES"):                     # A/B: BatchNorm values per workgroup budget (cnn_kernels)
     from gentun_amd.ops import cnn_kernels as _K
     _K.BN_CHUNK_VALUES = int(os.environ["BNVALUES"])
 if os.environ.get("BNCHUNK") == "old":             # A/B: BatchNorm chunks of 512 pixels for every shape (round 5)
