@@ -18,6 +18,9 @@
 // early-stopping check), each fold on its own thread. Deterministic: all
 // sampling comes from a splitmix64 stream keyed by (seed, fold, round, class).
 // What the MI355X engine (csrc/hip/gbdt_hist.hip) shares with this one: cv_protocol.h.
+//
+// gbdt_train fits the final model with the same tree-growing step (one fold, no test rows) and hands out its
+// trees with float thresholds; gbdt_predict scores raw rows with them (gentun_amd/models/booster.py).
 
 #include <algorithm>
 #include <atomic>
@@ -41,13 +44,14 @@ struct Quantized {
   int n = 0, F = 0;
   std::vector<uint8_t> bins;            // row-major [n][F]
   std::vector<int> nbins;               // per feature
+  std::vector<std::vector<float>> upper;   // per feature: bin b holds values <= upper[b] (gbdt_train's thresholds)
 };
 
 // One feature column -> bins (exact: <= kMaxBin distinct values keep one bin
 // each, otherwise kMaxBin equal-count quantile cuts). Writes bin b of row i
-// at out[i * stride].
+// at out[i * stride] (out may be null: cuts only) and hands out the bins' upper bounds.
 static int quantize_column(const float* X, int n, int F, int f, uint8_t* out, size_t stride,
-                           std::vector<float>& col, std::vector<float>& sorted) {
+                           std::vector<float>& col, std::vector<float>& sorted, std::vector<float>& upper) {
   for (int i = 0; i < n; ++i) {
     float v = X[(size_t)i * F + f];
     col[i] = std::isnan(v) ? -std::numeric_limits<float>::infinity() : v;
@@ -61,7 +65,7 @@ static int quantize_column(const float* X, int n, int F, int f, uint8_t* out, si
       uniq.push_back(sorted[i]);
       if ((int)uniq.size() > kMaxBin) break;
     }
-  std::vector<float> upper;           // bin b holds values <= upper[b]
+  upper.clear();                      // bin b holds values <= upper[b]
   if ((int)uniq.size() <= kMaxBin) {
     upper = uniq;
   } else {
@@ -74,7 +78,7 @@ static int quantize_column(const float* X, int n, int F, int f, uint8_t* out, si
     }
     upper.back() = sorted[n - 1];
   }
-  for (int i = 0; i < n; ++i) {
+  for (int i = 0; out != nullptr && i < n; ++i) {
     int b = (int)(std::lower_bound(upper.begin(), upper.end(), col[i]) - upper.begin());
     if (b >= (int)upper.size()) b = (int)upper.size() - 1;
     out[(size_t)i * stride] = (uint8_t)b;
@@ -85,14 +89,18 @@ static int quantize_column(const float* X, int n, int F, int f, uint8_t* out, si
 // Columns are independent: one thread per stripe of features (the per-column
 // sort dominates: ~n log n per feature). feature_major: bins[f][n] (the GPU
 // histogram layout) instead of bins[n][F].
-static void quantize_into(const float* X, int n, int F, uint8_t* bins, int* nbins, bool feature_major) {
+// uppers (optional): F vectors that receive every feature's upper bounds; bins may be null with it (cuts only).
+static void quantize_into(const float* X, int n, int F, uint8_t* bins, int* nbins, bool feature_major,
+                          std::vector<float>* uppers = nullptr) {
   int nt = (int)std::max(1u, std::thread::hardware_concurrency());
   nt = std::min(nt, std::max(1, F));
   auto work = [&](int t) {
-    std::vector<float> col(n), sorted;
-    for (int f = t; f < F; f += nt)
-      nbins[f] = feature_major ? quantize_column(X, n, F, f, bins + (size_t)f * n, 1, col, sorted)
-                               : quantize_column(X, n, F, f, bins + f, (size_t)F, col, sorted);
+    std::vector<float> col(n), sorted, upper;
+    for (int f = t; f < F; f += nt) {
+      uint8_t* out = bins == nullptr ? nullptr : (feature_major ? bins + (size_t)f * n : bins + f);
+      nbins[f] = quantize_column(X, n, F, f, out, feature_major ? 1 : (size_t)F, col, sorted, upper);
+      if (uppers) uppers[f] = upper;
+    }
   };
   if (nt == 1 || (size_t)n * F < (1u << 16)) {
     nt = 1;
@@ -109,7 +117,8 @@ Quantized quantize(const float* X, int n, int F) {
   q.n = n; q.F = F;
   q.bins.resize((size_t)n * F);
   q.nbins.resize(F);
-  quantize_into(X, n, F, q.bins.data(), q.nbins.data(), false);
+  q.upper.resize(F);
+  quantize_into(X, n, F, q.bins.data(), q.nbins.data(), false, q.upper.data());
   return q;
 }
 
@@ -297,6 +306,67 @@ double eval_metric(int metric, int obj, int K, const std::vector<int>& rows, con
   return 0.0;
 }
 
+// One class tree of one booster (gbdt_cv: class c of a fold's round; gbdt_train: of the final model's round):
+// the tree's draws from its stream, gradients of the training rows at the current margins, the row sample,
+// the tree, and its leaf values added to the margins of every row.
+Tree grow_class_tree(const Quantized& q, const float* y, const std::vector<int>& train, std::vector<double>& margin,
+                     const Params& p, int objective, int K, int c, uint64_t fold_round) {
+  const int n = q.n, F = q.F;
+  const bool multi = (objective == OBJ_MULTI_SOFTMAX || objective == OBJ_MULTI_SOFTPROB);
+  Rng rng(class_stream(fold_round, c));
+  const TreeDraws draws = draw_tree(rng, p, F);
+  std::vector<GH> gh(n, GH{0.0, 0.0});
+  for (int i : train) {
+    const double* m = &margin[(size_t)i * K];
+    double g, h;
+    if (objective == OBJ_SQUARED) { g = m[0] - y[i]; h = 1.0; }
+    else if (!multi) {
+      const double pr = sigmoid(m[0]);
+      g = pr - y[i]; h = std::max(pr * (1 - pr), 1e-16);
+      if (y[i] > 0.5 && objective != OBJ_LOGISTIC) { g *= p.scale_pos_weight; h *= p.scale_pos_weight; }
+    } else {
+      double mx = m[0];
+      for (int j = 1; j < K; ++j) mx = std::max(mx, m[j]);
+      double z = 0;
+      for (int j = 0; j < K; ++j) z += std::exp(m[j] - mx);
+      const double pr = std::exp(m[c] - mx) / z;
+      g = pr - ((int)y[i] == c ? 1.0 : 0.0); h = std::max(2.0 * pr * (1 - pr), 1e-16);
+    }
+    gh[i] = GH{g, h};
+  }
+  std::vector<int> rows;
+  rows.reserve(train.size());
+  if (p.subsample < 1.0) {
+    // the GPU path (csrc/hip/gbdt_hist.hip root_rows_kernel) samples the same rows in parallel
+    for (int i : train) if (row_uniform(draws.row_key, (uint64_t)i) < p.subsample) rows.push_back(i);
+  } else {
+    rows = train;
+  }
+  Tree t = build_tree(q, gh, rows, p, draws);
+  for (int i = 0; i < n; ++i) margin[(size_t)i * K + c] += t.predict(&q.bins[(size_t)i * F]);
+  return t;
+}
+
+// A fitted model's trees in the compact layout of gentun_amd/models/booster.py: tree t's nodes are
+// [offsets[t], offsets[t + 1]), numbered in level order (build_tree's creation order), right child = left + 1.
+struct Forest {
+  std::vector<long long> offsets{0};
+  std::vector<int> feature, split_bin, left;
+  std::vector<float> threshold;
+  std::vector<double> value;
+  void add(const Tree& t, const Quantized& q) {
+    for (const Node& nd : t.nodes) {
+      const bool leaf = nd.left < 0;
+      feature.push_back(leaf ? -1 : nd.feature);
+      split_bin.push_back(leaf ? -1 : nd.split_bin);
+      left.push_back(leaf ? -1 : nd.left);
+      threshold.push_back(leaf ? 0.f : q.upper[nd.feature][nd.split_bin]);
+      value.push_back(nd.value);
+    }
+    offsets.push_back((long long)feature.size());
+  }
+};
+
 }  // namespace
 
 extern "C" {
@@ -333,39 +403,7 @@ int gbdt_cv(const float* X, int n, int F, const float* y, const int* fold_of, in
   auto round_fold = [&](int k, int round) {
     FoldState& fs = folds[k];
     const uint64_t fold_round = fold_round_seed(seed, k, round);
-    for (int c = 0; c < K; ++c) {
-      Rng rng(class_stream(fold_round, c));
-      const TreeDraws draws = draw_tree(rng, p, F);
-      std::vector<GH> gh(n, GH{0.0, 0.0});
-      for (int i : fs.train) {
-        const double* m = &fs.margin[(size_t)i * K];
-        double g, h;
-        if (objective == OBJ_SQUARED) { g = m[0] - y[i]; h = 1.0; }
-        else if (!multi) {
-          const double pr = sigmoid(m[0]);
-          g = pr - y[i]; h = std::max(pr * (1 - pr), 1e-16);
-          if (y[i] > 0.5 && objective != OBJ_LOGISTIC) { g *= p.scale_pos_weight; h *= p.scale_pos_weight; }
-        } else {
-          double mx = m[0];
-          for (int j = 1; j < K; ++j) mx = std::max(mx, m[j]);
-          double z = 0;
-          for (int j = 0; j < K; ++j) z += std::exp(m[j] - mx);
-          const double pr = std::exp(m[c] - mx) / z;
-          g = pr - ((int)y[i] == c ? 1.0 : 0.0); h = std::max(2.0 * pr * (1 - pr), 1e-16);
-        }
-        gh[i] = GH{g, h};
-      }
-      std::vector<int> rows;
-      rows.reserve(fs.train.size());
-      if (p.subsample < 1.0) {
-        // the GPU path (csrc/hip/gbdt_hist.hip root_rows_kernel) samples the same rows in parallel
-        for (int i : fs.train) if (row_uniform(draws.row_key, (uint64_t)i) < p.subsample) rows.push_back(i);
-      } else {
-        rows = fs.train;
-      }
-      Tree t = build_tree(q, gh, rows, p, draws);
-      for (int i = 0; i < n; ++i) fs.margin[(size_t)i * K + c] += t.predict(&q.bins[(size_t)i * F]);
-    }
+    for (int c = 0; c < K; ++c) grow_class_tree(q, y, fs.train, fs.margin, p, objective, K, c, fold_round);
     for (int m = 0; m < n_metrics; ++m) {
       train_vals[(size_t)m * nfold + k] = eval_metric(metrics[m], objective, K, fs.train, fs.margin, y);
       test_vals[(size_t)m * nfold + k] = eval_metric(metrics[m], objective, K, fs.test, fs.margin, y);
@@ -390,6 +428,110 @@ int gbdt_cv(const float* X, int n, int F, const float* y, const int* fold_of, in
     if (stop.update(round, out_hist[((size_t)round * n_metrics + (n_metrics - 1)) * 4 + 2])) break;
   }
   return stop.kept_rows(rounds_done);
+}
+
+// Fit the final model: the cv protocol with one fold (index 0) and no test rows, every row a training row, so
+// the streams are fold_round_seed(seed, 0, round). out_hist [num_boost_round][n_metrics]: the train metrics;
+// out_margin (may be null) [n][K]: the final fp64 margins. *out_forest receives a handle for
+// gbdt_forest_size / gbdt_forest_copy / gbdt_forest_free. Returns the number of rounds, or < 0 on error.
+int gbdt_train(const float* X, int n, int F, const float* y, const double* params, int objective, int num_class,
+               const int* metrics, int n_metrics, int num_boost_round, unsigned long long seed, double* out_hist,
+               double* out_margin, void** out_forest) {
+  if (n <= 0 || F <= 0 || n_metrics <= 0 || num_boost_round < 0 || out_forest == nullptr) return -1;
+  Params p;
+  std::memcpy(&p, params, sizeof(Params));
+  const bool multi = (objective == OBJ_MULTI_SOFTMAX || objective == OBJ_MULTI_SOFTPROB);
+  const int K = multi ? std::max(2, num_class) : 1;
+  const Quantized q = quantize(X, n, F);
+  std::vector<int> train(n);
+  std::iota(train.begin(), train.end(), 0);
+  std::vector<double> margin((size_t)n * K, base_margin(objective, p.base_score));
+  Forest* forest = new Forest();
+  for (int round = 0; round < num_boost_round; ++round) {
+    const uint64_t fold_round = fold_round_seed(seed, 0, round);
+    for (int c = 0; c < K; ++c) forest->add(grow_class_tree(q, y, train, margin, p, objective, K, c, fold_round), q);
+    for (int m = 0; m < n_metrics; ++m)
+      out_hist[(size_t)round * n_metrics + m] = eval_metric(metrics[m], objective, K, train, margin, y);
+  }
+  if (out_margin) std::memcpy(out_margin, margin.data(), sizeof(double) * margin.size());
+  *out_forest = forest;
+  return num_boost_round;
+}
+
+// sizes[0] = trees, sizes[1] = nodes
+int gbdt_forest_size(const void* forest, long long* sizes) {
+  const Forest* f = static_cast<const Forest*>(forest);
+  sizes[0] = (long long)f->offsets.size() - 1;
+  sizes[1] = (long long)f->feature.size();
+  return 0;
+}
+
+int gbdt_forest_copy(const void* forest, long long* offsets, int* feature, float* threshold, int* split_bin, int* left,
+                     double* value) {
+  const Forest* f = static_cast<const Forest*>(forest);
+  const size_t N = f->feature.size();
+  std::memcpy(offsets, f->offsets.data(), sizeof(long long) * f->offsets.size());
+  if (N == 0) return 0;
+  std::memcpy(feature, f->feature.data(), sizeof(int) * N);
+  std::memcpy(threshold, f->threshold.data(), sizeof(float) * N);
+  std::memcpy(split_bin, f->split_bin.data(), sizeof(int) * N);
+  std::memcpy(left, f->left.data(), sizeof(int) * N);
+  std::memcpy(value, f->value.data(), sizeof(double) * N);
+  return 0;
+}
+
+void gbdt_forest_free(void* forest) { delete static_cast<Forest*>(forest); }
+
+// Predict on raw float rows with a compact forest (tree t: round t / K, class t % K; the first ntrees trees).
+// A row goes left when !(x[feature] > threshold) (NaN goes left, as in training); the margin of (row, class) is
+// base plus that class's leaf values, added one tree at a time in tree order in fp64. Rows are split over
+// nthreads; every (row, class) is summed by one thread in the same order, so the result does not depend on the
+// thread count. out_margin [n][K] and out_leaf [n][ntrees] (tree-local leaf indices) may each be null.
+int gbdt_predict(const float* X, int n, int F, const long long* offsets, const int* feature, const float* threshold,
+                 const int* left, const double* value, int ntrees, int K, double base, int nthreads,
+                 double* out_margin, int* out_leaf) {
+  if (n < 0 || F <= 0 || K <= 0 || ntrees < 0) return -1;
+  for (int t = 0; t < ntrees; ++t)            // a corrupt file must not walk out of bounds
+    for (long long j = offsets[t]; j < offsets[t + 1]; ++j) {
+      const long long sz = offsets[t + 1] - offsets[t];
+      if (feature[j] >= F) return -2;
+      if (feature[j] >= 0 && (left[j] <= j - offsets[t] || left[j] + 1 >= sz)) return -2;
+    }
+  if (nthreads <= 0) nthreads = (int)std::max(1u, std::thread::hardware_concurrency());
+  nthreads = std::max(1, std::min(nthreads, n / 256));
+  auto work = [&](int i0, int i1) {
+    for (int i = i0; i < i1; ++i) {
+      const float* row = X + (size_t)i * F;
+      if (out_margin)
+        for (int c = 0; c < K; ++c) out_margin[(size_t)i * K + c] = base;
+      for (int t = 0; t < ntrees; ++t) {
+        const long long o = offsets[t];
+        int j = 0;
+        while (feature[o + j] >= 0) j = !(row[feature[o + j]] > threshold[o + j]) ? left[o + j] : left[o + j] + 1;
+        if (out_margin) out_margin[(size_t)i * K + t % K] += value[o + j];
+        if (out_leaf) out_leaf[(size_t)i * ntrees + t] = j;
+      }
+    }
+  };
+  if (nthreads == 1) {
+    work(0, n);
+    return 0;
+  }
+  std::vector<std::thread> th;
+  for (int t = 0; t < nthreads; ++t)
+    th.emplace_back(work, (int)((long long)n * t / nthreads), (int)((long long)n * (t + 1) / nthreads));
+  for (auto& x : th) x.join();
+  return 0;
+}
+
+// Per-feature upper bounds of the quantiser's bins: nbins_out [F], upper_out [F][256] (the first nbins[f] of
+// feature f's row are set). bin = min(lower_bound(upper, v with NaN -> -inf), nbins - 1).
+int gbdt_cuts(const float* X, int n, int F, int* nbins_out, float* upper_out) {
+  if (n <= 0 || F <= 0) return -1;
+  std::vector<std::vector<float>> up(F);
+  quantize_into(X, n, F, nullptr, nbins_out, false, up.data());
+  for (int f = 0; f < F; ++f) std::copy(up[f].begin(), up[f].end(), upper_out + (size_t)f * kMaxBin);
+  return 0;
 }
 
 // Quantise only (exposed for the HIP path and tests): bins out [n][F], nbins out [F].

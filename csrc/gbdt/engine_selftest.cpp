@@ -26,6 +26,17 @@ int gbdt_cv(const float* X, int n, int F, const float* y, const int* fold_of, in
             int early_stopping_rounds, unsigned long long seed, int nthreads, double* out_hist);
 int gbdt_quantize(const float* X, int n, int F, uint8_t* bins_out, int* nbins_out);
 int gbdt_quantize_fm(const float* X, int n, int F, uint8_t* bins_out, int* nbins_out);
+int gbdt_train(const float* X, int n, int F, const float* y, const double* params, int objective, int num_class,
+               const int* metrics, int n_metrics, int num_boost_round, unsigned long long seed, double* out_hist,
+               double* out_margin, void** out_forest);
+int gbdt_forest_size(const void* forest, long long* sizes);
+int gbdt_forest_copy(const void* forest, long long* offsets, int* feature, float* threshold, int* split_bin, int* left,
+                     double* value);
+void gbdt_forest_free(void* forest);
+int gbdt_predict(const float* X, int n, int F, const long long* offsets, const int* feature, const float* threshold,
+                 const int* left, const double* value, int ntrees, int K, double base, int nthreads,
+                 double* out_margin, int* out_leaf);
+int gbdt_cuts(const float* X, int n, int F, int* nbins_out, float* upper_out);
 }
 
 namespace {
@@ -156,11 +167,84 @@ void protocol_stats_and_stopping() {
   }
 }
 
+// gbdt_train -> compact forest -> gbdt_predict: the final margins of the training run, whatever the thread
+// count; ntree_limit; leaf indices inside their trees; thresholds = the cuts at the split bins.
+void train_predict(const Data& d, const double* p, int obj, int ncls, int metric, int rounds) {
+  const int K = ncls > 0 ? ncls : 1;
+  std::vector<double> hist(rounds, -1.0), margin(size_t(d.n) * K);
+  void* forest = nullptr;
+  check(gbdt_train(d.X.data(), d.n, d.F, d.y.data(), p, obj, ncls, &metric, 1, rounds, 99ull, hist.data(),
+                   margin.data(), &forest) == rounds && forest != nullptr, "gbdt_train rc");
+  if (forest == nullptr) return;
+  for (double v : hist) check(std::isfinite(v), "train metric finite");
+  long long sz[2];
+  gbdt_forest_size(forest, sz);
+  check(sz[0] == (long long)rounds * K && sz[1] >= sz[0], "forest size");
+  const size_t T = size_t(sz[0]), N = size_t(sz[1]);
+  std::vector<long long> off(T + 1);
+  std::vector<int> feat(N), sbin(N), left(N);
+  std::vector<float> thr(N);
+  std::vector<double> val(N);
+  gbdt_forest_copy(forest, off.data(), feat.data(), thr.data(), sbin.data(), left.data(), val.data());
+  gbdt_forest_free(forest);
+  check(off[0] == 0 && off[T] == (long long)N, "forest offsets");
+  if (p[2] == 0) check(N == T, "depth 0: one leaf per tree");
+  std::vector<int> nb(d.F);
+  std::vector<float> upper(size_t(d.F) * 256);
+  check(gbdt_cuts(d.X.data(), d.n, d.F, nb.data(), upper.data()) == 0, "gbdt_cuts rc");
+  for (size_t j = 0; j < N; ++j)
+    if (feat[j] >= 0) {
+      check(feat[j] < d.F && sbin[j] >= 0 && sbin[j] + 1 < nb[feat[j]], "split bin below the last bin");
+      check(thr[j] == upper[size_t(feat[j]) * 256 + sbin[j]], "threshold = upper[split_bin]");
+    }
+  const double base = gbdt::base_margin(obj, p[11]);
+  std::vector<double> m1(margin.size()), m4(margin.size());
+  check(gbdt_predict(d.X.data(), d.n, d.F, off.data(), feat.data(), thr.data(), left.data(), val.data(), int(T), K, base,
+                     1, m1.data(), nullptr) == 0, "gbdt_predict rc");
+  check(gbdt_predict(d.X.data(), d.n, d.F, off.data(), feat.data(), thr.data(), left.data(), val.data(), int(T), K, base,
+                     4, m4.data(), nullptr) == 0, "gbdt_predict rc, 4 threads");
+  check(std::memcmp(m1.data(), margin.data(), sizeof(double) * margin.size()) == 0, "predict = training margins");
+  check(std::memcmp(m1.data(), m4.data(), sizeof(double) * margin.size()) == 0, "predict does not depend on threads");
+  // ntree_limit: the first round only, margins and leaves together
+  std::vector<int> leaf(size_t(d.n) * K);
+  check(gbdt_predict(d.X.data(), d.n, d.F, off.data(), feat.data(), thr.data(), left.data(), val.data(), K, K, base, 3,
+                     m4.data(), leaf.data()) == 0, "gbdt_predict rc, one round");
+  bool ok = true;
+  for (int i = 0; i < d.n; ++i)
+    for (int c = 0; c < K; ++c) {
+      const int j = leaf[size_t(i) * K + c];
+      ok = ok && j >= 0 && j < off[c + 1] - off[c] && feat[off[c] + j] < 0 && m4[size_t(i) * K + c] == base + val[off[c] + j];
+    }
+  check(ok, "one round: margin = base + the leaf's value");
+  // rows the model never saw: NaN, infinities, out of range
+  std::vector<float> odd(size_t(4) * d.F, NAN);
+  for (int f = 0; f < d.F; ++f) { odd[d.F + f] = INFINITY; odd[2 * d.F + f] = -INFINITY; odd[3 * d.F + f] = 1e30f; }
+  std::vector<double> mo(size_t(4) * K);
+  check(gbdt_predict(odd.data(), 4, d.F, off.data(), feat.data(), thr.data(), left.data(), val.data(), int(T), K, base, 2,
+                     mo.data(), nullptr) == 0, "gbdt_predict rc, odd rows");
+  for (double v : mo) check(std::isfinite(v), "odd rows: finite margins");
+}
+
 }  // namespace
 
 int main() {
   protocol_sampling();
   protocol_stats_and_stopping();
+  // the final model: regression with sampling and a NaN column, multi-class, binary, depth 0
+  {
+    Data d = make(2500, 7, 0, 1, 6);
+    for (int i = 0; i < d.n; ++i) d.X[size_t(i) * d.F + 3] = NAN;
+    double p[12];
+    std::memcpy(p, P_default, sizeof p);
+    p[2] = 5; p[5] = 0.7; p[6] = 0.7; p[7] = 0.6;
+    train_predict(d, p, 0, 0, 0, 4);
+    p[2] = 0;
+    train_predict(d, p, 0, 0, 0, 2);
+    Data m = make(1500, 5, 2, 1, 7);
+    train_predict(m, P_default, 5, 3, 6, 3);
+    Data b = make(1200, 6, 1, 1, 8);
+    train_predict(b, P_default, 2, 0, 2, 3);
+  }
   // quantiser, both layouts
   {
     Data d = make(5000, 13, 0, 5, 1);

@@ -11,6 +11,8 @@ namespace gbdt_cache {
 extern uint8_t* bins;      // row-major [n][Fs] uint8
 extern long long key;      // 0 = empty
 extern size_t bytes;
+extern float* upper;       // the quantiser's cuts of `key`, [upper_F][256] float (null: bins uploaded by the host)
+extern int upper_F;
 extern std::mutex mu;
 void invalidate_derived();   // drop copies derived from bins (gbdt_hist.hip's feature-major copy); call with mu held
 }  // namespace gbdt_cache

@@ -902,6 +902,8 @@ namespace gbdt_cache {
 uint8_t* bins = nullptr;
 long long key = 0;
 size_t bytes = 0;
+float* upper = nullptr;
+int upper_F = 0;
 std::mutex mu;
 // feature-major copy of the cached bins (partition), rebuilt when the cache changes
 static struct { uint8_t* bins = nullptr; const uint8_t* src = nullptr; long long key = 0; size_t bytes = 0; } binsT;
@@ -937,6 +939,13 @@ enum : unsigned {
   GT_MET = 1u << 18,     // double [n_metrics][nfold][mblocks][4] partial sums
   GT_AUC = 1u << 19,     // double [nfold][4]: train rank sum, train positives, test rank sum, test positives
 };
+
+// ---- tree sink (gbdt_train_hip): every grown tree's heap tables reach the host with the round's blocking
+// metric read-back. Without a sink (gbdt_cv_hip, gbdt_cv_hip_trace) no launch, copy or synchronisation is
+// added, the tracer's rule. tree: int2 [2^(D+1) - 1] (feature, split bin), feature -1 = leaf, heap-indexed
+// (children of i: 2i + 1, 2i + 2); entries the walk from the root does not reach are stale.
+extern "C" typedef void (*gbdt_tree_fn)(void* user, int round, int cls, const int* tree_xy, const float* leaf,
+                                        int tsz, int max_depth);
 
 namespace {
 
@@ -987,7 +996,9 @@ int ensure_bins(const uint8_t* bins_h, int n, int Fs, long long cache_key) {
   if (cache_key == 0 || cache_key != gbdt_cache::key || gbdt_cache::bytes != nbytes || gbdt_cache::bins == nullptr) {
     if (bins_h == nullptr) return -7;
     if (gbdt_cache::bins) (void)hipFree(gbdt_cache::bins);
+    if (gbdt_cache::upper) (void)hipFree(gbdt_cache::upper);       // host bins come without cuts
     gbdt_cache::bins = nullptr; gbdt_cache::key = 0; gbdt_cache::bytes = 0;
+    gbdt_cache::upper = nullptr; gbdt_cache::upper_F = 0;
     if (hipMalloc(&gbdt_cache::bins, nbytes) != hipSuccess) return -100;
     if (hipMemcpy(gbdt_cache::bins, bins_h, nbytes, hipMemcpyHostToDevice) != hipSuccess) return -100;
     gbdt_cache::key = cache_key; gbdt_cache::bytes = nbytes;
@@ -1005,6 +1016,8 @@ int ensure_bins(const uint8_t* bins_h, int n, int Fs, long long cache_key) {
 // One CV call: geometry, launch shapes, buffers and the steps of a round (each returns 0 or -100 - hipError)
 struct CvRun {
   Params p; int objective, n_metrics; const int* metrics; u64 seed; Tracer tr;
+  gbdt_tree_fn tree_sink = nullptr; void* tree_user = nullptr;   // fold 0's trees (gbdt_train_hip: the only fold)
+  int2* h_tree = nullptr; float* h_leaf = nullptr;               // pinned [K][tsz], only with a tree sink
   int n, F, Fs, nfold, K, D;
   int obj;                 // grad_kernel's code: 0 squared error, 1 reg:logistic, 2 binary, 3 multi-class
   bool hconst, want_auc;   // hconst: h = 1 for every row -> count histograms for the hessian (hist_kernel<true>)
@@ -1101,6 +1114,10 @@ struct CvRun {
     }
     HC(ws.alloc_pinned(h_up, keys_bytes + sizeof(int) * K * order_elems));
     HC(ws.alloc_pinned(h_met, sizeof(double) * met_elems));
+    if (tree_sink) {
+      HC(ws.alloc_pinned(h_tree, sizeof(int2) * (size_t)K * tsz));
+      HC(ws.alloc_pinned(h_leaf, sizeof(float) * (size_t)K * tsz));
+    }
     HC(hipMemcpy(d_y, y_h, sizeof(float) * n, hipMemcpyHostToDevice));
     HC(hipMemcpy(d_fold, fold_h, sizeof(int) * n, hipMemcpyHostToDevice));
     HC(hipMemcpy(d_nb, nbins_h, sizeof(int) * F, hipMemcpyHostToDevice));
@@ -1203,6 +1220,21 @@ struct CvRun {
     return 0;
   }
 
+  // With a tree sink: queue the copy of fold 0's tree of class c behind its kernels (the next tree overwrites
+  // d_tree / d_leaf); read_metrics' blocking copy waits for it.
+  int stash_tree(int c) {
+    if (!tree_sink) return 0;
+    HC(hipMemcpyAsync(h_tree + (size_t)c * tsz, d_tree, sizeof(int2) * tsz, hipMemcpyDeviceToHost, 0));
+    HC(hipMemcpyAsync(h_leaf + (size_t)c * tsz, d_leaf, sizeof(float) * tsz, hipMemcpyDeviceToHost, 0));
+    return 0;
+  }
+  void hand_out_trees(int round) const {
+    if (!tree_sink) return;
+    for (int c = 0; c < K; ++c)
+      tree_sink(tree_user, round, c, reinterpret_cast<const int*>(h_tree + (size_t)c * tsz), h_leaf + (size_t)c * tsz,
+                tsz, D);
+  }
+
   // The round's metric launches and its blocking copies: early stopping needs the test metric.
   int read_metrics(int round) {
     for (int mi = 0; mi < n_metrics; ++mi)
@@ -1249,23 +1281,11 @@ struct CvRun {
   }
 };
 
-}  // namespace
-
-extern "C" {
-
-// Same contract as gbdt_cv (csrc/gbdt/engine.cpp) for every objective (reg:linear/squarederror, reg:logistic,
-// binary:logistic/logitraw, multi:softmax/softprob: one tree per class) and every metric (rmse, mae, logloss,
-// error, auc, merror, mlogloss; early stopping on the last, auc maximised). auc needs nfold <= 32 (64 sort
-// segments). bins_h may be null when gbdt_quantize_hip already left the dataset's bins on the device under
-// cache_key (returns -7 if they were evicted). bins: ROW-major [n][Fs] uint8 (Fs >= F, Fs % 4 == 0).
-// cache_key != 0 keeps the device copy of the bins across calls for the same key (one dataset, many candidates).
-// With the stage trace: the first trace_rounds rounds hand the buffers selected by trace_mask (GT_* bits) to
-// sink. Same computation and return value with and without.
-int gbdt_cv_hip_trace(const uint8_t* bins_h, int Fs, const int* nbins_h, int n, int F, const float* y_h,
-                      const int* fold_h, int nfold, const double* P, int objective, int num_class,
-                      const int* metrics, int n_metrics, int num_boost_round, int early_stopping_rounds,
-                      unsigned long long seed, long long cache_key, double* out_hist, int trace_rounds,
-                      unsigned trace_mask, gbdt_trace_fn sink, void* user) {
+// One CV call of either entry point. tree_sink / out_margin (fold 0's final fp32 margins [n][K]) may be null.
+int run_cv(const uint8_t* bins_h, int Fs, const int* nbins_h, int n, int F, const float* y_h, const int* fold_h,
+           int nfold, const double* P, int objective, int num_class, const int* metrics, int n_metrics,
+           int num_boost_round, int early_stopping_rounds, unsigned long long seed, long long cache_key,
+           double* out_hist, Tracer tr, gbdt_tree_fn tree_sink, void* tree_user, float* out_margin) {
   if (objective < OBJ_SQUARED || objective > OBJ_MULTI_SOFTPROB || n_metrics < 1 || Fs % 4 || Fs < F || n <= 0 ||
       nfold <= 0 || F <= 0)
     return -1;
@@ -1283,7 +1303,7 @@ int gbdt_cv_hip_trace(const uint8_t* bins_h, int Fs, const int* nbins_h, int n, 
   CvRun r;
   std::memcpy(&r.p, P, sizeof(Params));
   r.objective = objective; r.metrics = metrics; r.n_metrics = n_metrics; r.seed = seed; r.want_auc = want_auc;
-  r.tr = Tracer{sink, user, trace_rounds, trace_mask};
+  r.tr = tr; r.tree_sink = tree_sink; r.tree_user = tree_user;
   r.shape(n, F, Fs, nfold, num_class, fold_h);
   if (int rc = ensure_bins(bins_h, n, Fs, cache_key)) return rc;
   r.d_bins = gbdt_cache::bins; r.d_binsT = gbdt_cache::binsT.bins;
@@ -1292,9 +1312,12 @@ int gbdt_cv_hip_trace(const uint8_t* bins_h, int Fs, const int* nbins_h, int n, 
   int rounds_done = 0;
   for (int round = 0; round < num_boost_round; ++round) {
     if (int rc = r.draw_round(round)) return rc;
-    for (int c = 0; c < r.K; ++c)
+    for (int c = 0; c < r.K; ++c) {
       if (int rc = r.grow_tree(round, c)) return rc;
+      if (int rc = r.stash_tree(c)) return rc;
+    }
     if (int rc = r.read_metrics(round)) return rc;
+    r.hand_out_trees(round);
     const double tem_last = r.fold_stats(round, out_hist);
     rounds_done = round + 1;
     if (progress > 0 && rounds_done % progress == 0)
@@ -1304,7 +1327,30 @@ int gbdt_cv_hip_trace(const uint8_t* bins_h, int Fs, const int* nbins_h, int n, 
   if (timing)
     std::fprintf(stderr, "[gbdt_hip] %d rounds x %d folds in %.3f s (fold-batched device levels, depth %d)\n",
                  rounds_done, nfold, seconds(), r.D);
+  if (out_margin) HC(hipMemcpy(out_margin, r.d_margin, sizeof(float) * (size_t)n * r.K, hipMemcpyDeviceToHost));
   return stop.kept_rows(rounds_done);
+}
+
+}  // namespace
+
+extern "C" {
+
+// Same contract as gbdt_cv (csrc/gbdt/engine.cpp) for every objective (reg:linear/squarederror, reg:logistic,
+// binary:logistic/logitraw, multi:softmax/softprob: one tree per class) and every metric (rmse, mae, logloss,
+// error, auc, merror, mlogloss; early stopping on the last, auc maximised). auc needs nfold <= 32 (64 sort
+// segments). bins_h may be null when gbdt_quantize_hip already left the dataset's bins on the device under
+// cache_key (returns -7 if they were evicted). bins: ROW-major [n][Fs] uint8 (Fs >= F, Fs % 4 == 0).
+// cache_key != 0 keeps the device copy of the bins across calls for the same key (one dataset, many candidates).
+// With the stage trace: the first trace_rounds rounds hand the buffers selected by trace_mask (GT_* bits) to
+// sink. Same computation and return value with and without.
+int gbdt_cv_hip_trace(const uint8_t* bins_h, int Fs, const int* nbins_h, int n, int F, const float* y_h,
+                      const int* fold_h, int nfold, const double* P, int objective, int num_class,
+                      const int* metrics, int n_metrics, int num_boost_round, int early_stopping_rounds,
+                      unsigned long long seed, long long cache_key, double* out_hist, int trace_rounds,
+                      unsigned trace_mask, gbdt_trace_fn sink, void* user) {
+  return run_cv(bins_h, Fs, nbins_h, n, F, y_h, fold_h, nfold, P, objective, num_class, metrics, n_metrics,
+                num_boost_round, early_stopping_rounds, seed, cache_key, out_hist,
+                Tracer{sink, user, trace_rounds, trace_mask}, nullptr, nullptr, nullptr);
 }
 
 int gbdt_cv_hip(const uint8_t* bins_h, int Fs, const int* nbins_h, int n, int F, const float* y_h,
@@ -1313,6 +1359,28 @@ int gbdt_cv_hip(const uint8_t* bins_h, int Fs, const int* nbins_h, int n, int F,
                 long long cache_key, double* out_hist) {
   return gbdt_cv_hip_trace(bins_h, Fs, nbins_h, n, F, y_h, fold_h, nfold, P, objective, num_class, metrics, n_metrics,
                            num_boost_round, early_stopping_rounds, seed, cache_key, out_hist, 0, 0u, nullptr, nullptr);
+}
+
+// Fit the final model (gbdt_train of csrc/gbdt/engine.cpp): the CV loop with one fold and no test rows, the
+// dataset's bins already on the device under cache_key (gbdt_quantize_hip; -7 if evicted). Every tree of every
+// round is handed to sink as its heap tables; the host compacts them (there is no device forest buffer).
+// out_hist [num_boost_round][n_metrics]: the train metrics; out_margin (may be null): the final fp32 margins
+// [n][K]. -8: max_depth beyond GB_MAXD (cv clamps; a model that people keep must not). Returns the rounds.
+int gbdt_train_hip(int Fs, const int* nbins_h, int n, int F, const float* y_h, const double* P, int objective,
+                   int num_class, const int* metrics, int n_metrics, int num_boost_round, unsigned long long seed,
+                   long long cache_key, double* out_hist, gbdt_tree_fn sink, void* user, float* out_margin) {
+  if (sink == nullptr || n <= 0 || n_metrics < 1 || num_boost_round < 1) return -1;
+  Params p;
+  std::memcpy(&p, P, sizeof(Params));
+  if (p.max_depth > GB_MAXD) return -8;
+  const std::vector<int> fold(n, -1);
+  std::vector<double> hist4((size_t)num_boost_round * n_metrics * 4, 0.0);
+  const int rc = run_cv(nullptr, Fs, nbins_h, n, F, y_h, fold.data(), 1, P, objective, num_class, metrics, n_metrics,
+                        num_boost_round, 0, seed, cache_key, hist4.data(), Tracer{nullptr, nullptr, 0, 0u}, sink, user,
+                        out_margin);
+  if (rc < 0) return rc;
+  for (size_t i = 0; i < (size_t)num_boost_round * n_metrics; ++i) out_hist[i] = hist4[i * 4];
+  return rc;
 }
 
 // struct sizes and constants the trace's reader needs: sizeof LNode, Chunk, Red, SplitOut, NodeBest; GB_R,

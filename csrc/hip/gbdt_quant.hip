@@ -10,7 +10,9 @@
 //      stops after 257 values) or quantile cuts -> upper[F][256], nbins[F]
 //   4. binary search per (row, feature) -> row-major bins [n][Fs] written
 //      straight into the device bins cache (gbdt_cache.h) that the boosting
-//      kernels read: the quantised dataset never crosses PCIe.
+//      kernels read: the quantised dataset never crosses PCIe. upper[F][256]
+//      stays in the cache next to the bins: the thresholds of a GPU-trained
+//      booster come from it (gbdt_cuts_hip_copy).
 
 #include <hip/hip_runtime.h>
 
@@ -156,6 +158,9 @@ int gbdt_quantize_hip(const float* X_h, int n, int F, int Fs, long long cache_ke
   hipLaunchKernelGGL(qt_bins, dim3(2048), dim3(256), 0, 0, d_X, n, F, Fs, d_upper, d_nb, gbdt_cache::bins);
   QHC(hipGetLastError());
   QHC(hipMemcpy(nbins_out, d_nb, sizeof(int) * F, hipMemcpyDeviceToHost));
+  if (gbdt_cache::upper) (void)hipFree(gbdt_cache::upper);
+  gbdt_cache::upper = d_upper; gbdt_cache::upper_F = F;   // the cache owns the cuts from here on
+  d_upper = nullptr;
   gbdt_cache::key = cache_key;
 done:
   for (void* p : {(void*)d_X, (void*)d_col, (void*)d_sorted, (void*)d_upper, (void*)d_off, (void*)d_nb, d_tmp})
@@ -168,6 +173,15 @@ int gbdt_bins_hip_copy(long long cache_key, uint8_t* dst, size_t bytes) {
   std::lock_guard<std::mutex> lock(gbdt_cache::mu);
   if (cache_key == 0 || cache_key != gbdt_cache::key || bytes != gbdt_cache::bytes) return -7;
   return hipMemcpy(dst, gbdt_cache::bins, bytes, hipMemcpyDeviceToHost) == hipSuccess ? 0 : -3;
+}
+
+// Copy the cuts of the cached dataset back: dst [F][256] float, the first nbins[f] of row f are set.
+// -7 if the key is not resident (or its bins were uploaded by the host, without cuts).
+int gbdt_cuts_hip_copy(long long cache_key, float* dst) {
+  std::lock_guard<std::mutex> lock(gbdt_cache::mu);
+  if (cache_key == 0 || cache_key != gbdt_cache::key || gbdt_cache::upper == nullptr) return -7;
+  return hipMemcpy(dst, gbdt_cache::upper, sizeof(float) * (size_t)gbdt_cache::upper_F * 256, hipMemcpyDeviceToHost) ==
+                 hipSuccess ? 0 : -3;
 }
 
 }  // extern "C"

@@ -210,7 +210,19 @@ def cmd_xgb(args):
     extra = dict(nfold=args.nfold, num_boost_round=args.rounds, early_stopping_rounds=args.early_stopping,
                  objective=args.objective, eval_metric=args.metric,
                  device="cuda:{}".format(os.environ.get("LOCAL_RANK", "0")) if args.gpu else None)
-    return _run_search(args, XgboostIndividual, x, y, extra, maximize=False)
+    out = _run_search(args, XgboostIndividual, x, y, extra, maximize=False)
+    if out is not None and args.save_model:
+        # rank 0: refit the fittest individual's genes on all rows; the CV history gives the round count
+        from .models.xgboost_models import XgboostModel
+        model = XgboostModel(x, y, out["best_genes"], objective=args.objective, eval_metric=args.metric,
+                             nfold=args.nfold, num_boost_round=args.rounds, early_stopping_rounds=args.early_stopping,
+                             device=extra["device"])      # seed: the individuals' default, as in the search
+        model.cross_validate()
+        bst = model.fit()
+        bst.save(args.save_model)
+        print(json.dumps({"saved_model": args.save_model, "num_boost_round": bst.num_rounds,
+                          "num_trees": bst.num_trees}))
+    return out
 
 
 def cmd_info(_args):
@@ -276,6 +288,8 @@ def main(argv=None):
     x.add_argument("--objective", default="reg:linear")
     x.add_argument("--metric", default="rmse")
     x.add_argument("--gpu", action="store_true", help="run the GBDT histograms on the GPU")
+    x.add_argument("--save-model", default=None, metavar="PATH",
+                   help="after the search, refit the fittest individual on all rows and write the booster (.npz)")
     x.set_defaults(fn=cmd_xgb)
     i = sub.add_parser("info", help="build / device summary")
     i.set_defaults(fn=cmd_info)

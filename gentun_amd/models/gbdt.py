@@ -8,9 +8,14 @@ call site gentun/models/xgboost_models.py:32-37).
 
 Folds: shuffled, non-stratified k-fold with the given seed (xgboost 0.72
 ``cv`` defaults: ``shuffle=True``, ``stratified=False``, ``seed=0``).
+
+``train(params, x, y, num_boost_round, seed)`` fits the final model on all rows
+and returns a :class:`~gentun_amd.models.booster.Booster` (``xgb.train``);
+``cuts(x)`` are the quantiser's per-feature bin bounds.
 """
 
 import ctypes
+import math
 
 import numpy as np
 
@@ -65,10 +70,8 @@ def resolve_params(params):
     return p, OBJECTIVES[obj]
 
 
-def cv(params, x, y, num_boost_round=10, nfold=3, early_stopping_rounds=None, seed=0, device=None,
-       nthreads=0, folds=None):
-    x_key = x                     # dataset identity: the GPU path caches its bins per dataset
-    x, y = _as_arrays(x, y)
+def _setup(params, y):
+    """(engine params, objective code, num_class, metric names) of a cv / train call."""
     p, obj = resolve_params(params)
     num_class = int(params.get("num_class", 0) or 0)
     if obj in (4, 5) and num_class < 2:
@@ -78,6 +81,14 @@ def cv(params, x, y, num_boost_round=10, nfold=3, early_stopping_rounds=None, se
     for m in metrics:
         if m not in METRICS:
             raise ValueError("unsupported eval_metric {!r}".format(m))
+    return p, obj, num_class, metrics
+
+
+def cv(params, x, y, num_boost_round=10, nfold=3, early_stopping_rounds=None, seed=0, device=None,
+       nthreads=0, folds=None):
+    x_key = x                     # dataset identity: the GPU path caches its bins per dataset
+    x, y = _as_arrays(x, y)
+    p, obj, num_class, metrics = _setup(params, y)
     n = x.shape[0]
     if folds is None:
         folds = kfold(n, nfold, seed=seed)
@@ -117,3 +128,73 @@ def quantize(x):
     nb = np.zeros(f, np.int32)
     _lib.gbdt().gbdt_quantize(x.ctypes.data, n, f, bins.ctypes.data, nb.ctypes.data)
     return bins, nb
+
+
+def cuts(x):
+    """Per-feature upper bounds of the quantiser's bins, a list of float32 arrays:
+    ``bin = min(searchsorted(cuts[f], v with NaN -> -inf, 'left'), nbins[f] - 1)``."""
+    x, _ = _as_arrays(x, np.zeros(len(x)))
+    n, f = x.shape
+    nb = np.zeros(f, np.int32)
+    up = np.zeros((f, 256), np.float32)
+    if _lib.gbdt().gbdt_cuts(x.ctypes.data, n, f, nb.ctypes.data, up.ctypes.data) != 0:
+        raise RuntimeError("gbdt_cuts failed")
+    return [up[j, :nb[j]].copy() for j in range(f)]
+
+
+def base_margin(obj, base_score):
+    """cv_protocol.h base_margin: logit of base_score for the logistic objectives only."""
+    if obj not in (1, 2):
+        return float(base_score)
+    b = min(1 - 1e-7, max(1e-7, float(base_score)))
+    return math.log(b / (1 - b))          # libm's log, as std::log in the engines
+
+
+def train(params, x, y, num_boost_round=10, seed=0, device=None, nthreads=0, return_margin=False):
+    """Fit the final model on all rows (``xgb.train``): the engines' cv protocol with one fold and no test rows,
+    so ``history['train-<m>']`` equals ``cv(..., folds=[(all rows, [])])['train-<m>-mean']``. Parameters,
+    objectives, ``num_class`` inference and metrics are those of :func:`cv`. Returns a
+    :class:`~gentun_amd.models.booster.Booster` (with ``return_margin``: also the engine's final margins, fp64
+    ``[n, K]`` on the CPU, the fp32 training margins widened on the GPU). ``nthreads`` is accepted for symmetry
+    with :func:`cv`: one booster grows on one thread (the quantiser uses every core)."""
+    from .booster import Booster
+    x_key = x
+    x, y = _as_arrays(x, y)
+    p, obj, num_class, metrics = _setup(params, y)
+    K = max(2, num_class) if obj in (4, 5) else 1
+    n, F = x.shape
+    nrounds = int(num_boost_round)
+    if nrounds < 1:
+        raise ValueError("num_boost_round must be >= 1")
+    parr = np.array([p[k] for k in PARAM_ORDER], np.float64)
+    marr = np.array([METRICS[m] for m in metrics], np.int32)
+    hist = np.zeros((nrounds, len(metrics)), np.float64)
+    useed = seed & 0xFFFFFFFFFFFFFFFF
+    if device is not None and str(device).startswith("cuda"):
+        from . import gbdt_hip
+        arrays, margin = gbdt_hip.train(x, y, parr, obj, num_class, marr, nrounds, useed, hist, x_key=x_key,
+                                        return_margin=return_margin)
+    else:
+        lib = _lib.gbdt()
+        margin = np.zeros((n, K), np.float64) if return_margin else None
+        handle = ctypes.c_void_p()
+        rc = lib.gbdt_train(x.ctypes.data, n, F, y.ctypes.data, parr.ctypes.data, obj, num_class, marr.ctypes.data,
+                            len(metrics), nrounds, ctypes.c_ulonglong(useed), hist.ctypes.data,
+                            None if margin is None else margin.ctypes.data, ctypes.byref(handle))
+        if rc < 0:
+            raise RuntimeError("gbdt_train failed ({})".format(rc))
+        try:
+            sizes = np.zeros(2, np.int64)
+            lib.gbdt_forest_size(handle, sizes.ctypes.data)
+            nt, nn = int(sizes[0]), int(sizes[1])
+            arrays = {"tree_offsets": np.zeros(nt + 1, np.int64), "feature": np.zeros(nn, np.int32),
+                      "threshold": np.zeros(nn, np.float32), "split_bin": np.zeros(nn, np.int32),
+                      "left": np.zeros(nn, np.int32), "value": np.zeros(nn, np.float64)}
+            lib.gbdt_forest_copy(handle, *[arrays[k].ctypes.data for k in ("tree_offsets", "feature", "threshold",
+                                                                           "split_bin", "left", "value")])
+        finally:
+            lib.gbdt_forest_free(handle)
+    history = {"train-{}".format(m): hist[:, j].tolist() for j, m in enumerate(metrics)}
+    bst = Booster(objective=obj, num_class=K, base_margin=base_margin(obj, p["base_score"]), n_features=F,
+                  params=p, history=history, **arrays)
+    return (bst, margin) if return_margin else bst

@@ -230,3 +230,103 @@ def cv_trace(x, y, fold_of, nfold, parr, obj, num_class, marr, nrounds, esr, see
         if kept != -7:
             break
     return kept, blocks
+
+
+# ---- final model: training (gbdt_train_hip), device cuts, forest prediction (csrc/hip/gbdt_predict.hip) -------
+PREDICT_CHUNK_ROWS = 1 << 18      # rows per upload of Booster.predict(device='cuda...'); tests lower it
+_TREE_SINK = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+                              ctypes.c_int, ctypes.c_int)
+
+
+def device_cuts(key, nbins):
+    """The quantiser's cuts of the device-resident dataset ``key``: a list of float32 arrays (``gbdt.cuts``)."""
+    f = _lib.hip().gbdt_cuts_hip_copy
+    f.argtypes = [ctypes.c_longlong, ctypes.c_void_p]
+    f.restype = ctypes.c_int
+    up = np.zeros((len(nbins), 256), np.float32)
+    rc = f(key, up.ctypes.data)
+    if rc != 0:
+        raise RuntimeError("cuts of key {} not resident ({})".format(key, rc))
+    return [up[j, :nbins[j]].copy() for j in range(len(nbins))]
+
+
+def train(x, y, parr, obj, num_class, marr, nrounds, seed, hist, x_key=None, return_margin=False):
+    """``gbdt.train`` on the GPU: the cv loop with one fold and no test rows; every tree's heap tables come back
+    with the round's metric read-back and are compacted here to the Booster's level-order numbering, with
+    thresholds from the device quantiser's cuts. Returns ``(Booster arrays, margins or None)``."""
+    from .booster import compact_heap_tree
+    if not supported(obj, marr, 1):
+        raise ValueError("objective / metrics not supported by the GPU engine")
+    maxd = trace_layout()["GB_MAXD"]
+    if parr[2] > maxd:
+        raise ValueError("max_depth {:g} is beyond the GPU engine's deepest tree ({}): train on the CPU "
+                         "engine instead".format(parr[2], maxd))
+    f = _lib.hip().gbdt_train_hip
+    c = ctypes
+    f.argtypes = [c.c_int, c.c_void_p, c.c_int, c.c_int, c.c_void_p, c.c_void_p, c.c_int, c.c_int, c.c_void_p,
+                  c.c_int, c.c_int, c.c_ulonglong, c.c_longlong, c.c_void_p, _TREE_SINK, c.c_void_p, c.c_void_p]
+    f.restype = c.c_int
+    xk = x if x_key is None else x_key
+    y = np.ascontiguousarray(y.astype(np.float32))
+    marr = np.ascontiguousarray(marr.astype(np.int32))
+    n, F = x.shape
+    K = max(2, int(num_class)) if obj in (4, 5) else 1
+    margin32 = np.zeros((n, K), np.float32) if return_margin else None
+    trees = []
+
+    def sink(_user, _rnd, _cls, tree_p, leaf_p, tsz, max_depth):
+        txy = np.frombuffer(ctypes.string_at(tree_p, 8 * tsz), dtype="<i4").reshape(tsz, 2)
+        leaf = np.frombuffer(ctypes.string_at(leaf_p, 4 * tsz), dtype="<f4")
+        trees.append(compact_heap_tree(txy, leaf, max_depth))
+
+    cb = _TREE_SINK(sink)
+    for attempt in (0, 1):
+        del trees[:]
+        nb, key, fs = quantize_device(x, force=attempt > 0, ident=xk)
+        rc = f(fs, nb.ctypes.data, n, F, y.ctypes.data, parr.ctypes.data, int(obj), int(num_class), marr.ctypes.data,
+               len(marr), int(nrounds), ctypes.c_ulonglong(seed), key, hist.ctypes.data, cb, None,
+               None if margin32 is None else margin32.ctypes.data)
+        if rc != -7:                         # -7: another dataset evicted the device bins
+            break
+    if rc < 0:
+        raise RuntimeError("gbdt_train_hip failed ({})".format(rc))
+    upper = device_cuts(key, nb)
+    offsets, feature, split_bin, left, value, threshold = [0], [], [], [], [], []
+    for (tf, tb, tl, tv) in trees:
+        feature += tf
+        split_bin += tb
+        left += tl
+        value += tv
+        threshold += [float(upper[a][b]) if a >= 0 else 0.0 for a, b in zip(tf, tb)]
+        offsets.append(len(feature))
+    arrays = {"tree_offsets": offsets, "feature": feature, "threshold": threshold, "split_bin": split_bin,
+              "left": left, "value": value}
+    return arrays, (None if margin32 is None else margin32.astype(np.float64))
+
+
+def predict_rows(n_features):
+    """Rows per block that gbdt_predict.hip stages in LDS for this width (0: rows are read from global memory)."""
+    f = _lib.hip().gbdt_predict_hip_rows
+    f.argtypes = [ctypes.c_int]
+    f.restype = ctypes.c_int
+    return int(f(int(n_features)))
+
+
+def predict(bst, x, ntrees, out_margin, out_leaf, timing=None):
+    """Margins (fp64 ``[n, K]``) or leaf indices (int32 ``[n, ntrees]``) of ``x`` with the first ``ntrees`` trees
+    of ``bst`` on the GPU; bit-identical to the CPU predictor. ``timing``: a list that receives
+    ``[kernel ms, ms including transfers]``."""
+    f = _lib.hip().gbdt_predict_hip
+    c = ctypes
+    f.argtypes = [c.c_void_p, c.c_int, c.c_int, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_int,
+                  c.c_int, c.c_double, c.c_int, c.c_void_p, c.c_void_p, c.c_void_p]
+    f.restype = c.c_int
+    ms = np.zeros(2, np.float64)
+    rc = f(x.ctypes.data, x.shape[0], x.shape[1], bst.tree_offsets.ctypes.data, bst.feature.ctypes.data,
+           bst.threshold.ctypes.data, bst.left.ctypes.data, bst.value.ctypes.data, int(ntrees), bst.K,
+           bst.base_margin, int(PREDICT_CHUNK_ROWS), None if out_margin is None else out_margin.ctypes.data,
+           None if out_leaf is None else out_leaf.ctypes.data, ms.ctypes.data)
+    if rc != 0:
+        raise RuntimeError("gbdt_predict_hip failed ({})".format(rc))
+    if timing is not None:
+        timing[:] = ms.tolist()

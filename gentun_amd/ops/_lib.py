@@ -87,6 +87,21 @@ def gbdt():
         lib.gbdt_quantize.argtypes = [c.c_void_p, c.c_int, c.c_int, c.c_void_p, c.c_void_p]
         lib.gbdt_quantize_fm.restype = c.c_int
         lib.gbdt_quantize_fm.argtypes = [c.c_void_p, c.c_int, c.c_int, c.c_void_p, c.c_void_p]
+        lib.gbdt_cuts.restype = c.c_int
+        lib.gbdt_cuts.argtypes = [c.c_void_p, c.c_int, c.c_int, c.c_void_p, c.c_void_p]
+        lib.gbdt_train.restype = c.c_int
+        lib.gbdt_train.argtypes = [c.c_void_p, c.c_int, c.c_int, c.c_void_p, c.c_void_p, c.c_int, c.c_int,
+                                   c.c_void_p, c.c_int, c.c_int, c.c_ulonglong, c.c_void_p, c.c_void_p,
+                                   c.POINTER(c.c_void_p)]
+        lib.gbdt_forest_size.restype = c.c_int
+        lib.gbdt_forest_size.argtypes = [c.c_void_p, c.c_void_p]
+        lib.gbdt_forest_copy.restype = c.c_int
+        lib.gbdt_forest_copy.argtypes = [c.c_void_p] * 7
+        lib.gbdt_forest_free.restype = None
+        lib.gbdt_forest_free.argtypes = [c.c_void_p]
+        lib.gbdt_predict.restype = c.c_int
+        lib.gbdt_predict.argtypes = [c.c_void_p, c.c_int, c.c_int, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p,
+                                     c.c_void_p, c.c_int, c.c_int, c.c_double, c.c_int, c.c_void_p, c.c_void_p]
         lib._typed = True
     return lib
 
