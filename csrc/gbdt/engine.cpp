@@ -20,7 +20,9 @@
 // What the MI355X engine (csrc/hip/gbdt_hist.hip) shares with this one: cv_protocol.h.
 //
 // gbdt_train fits the final model with the same tree-growing step (one fold, no test rows) and hands out its
-// trees with float thresholds; gbdt_predict scores raw rows with them (gentun_amd/models/booster.py).
+// trees with float thresholds and their node statistics (cover, gain: gbdt_forest_stats); gbdt_predict scores
+// raw rows with them, gbdt_predict_contribs explains them (shap_tables.h, shared with csrc/hip/gbdt_shap.hip;
+// gentun_amd/models/booster.py).
 
 #include <algorithm>
 #include <atomic>
@@ -33,6 +35,7 @@
 #include <vector>
 
 #include "cv_protocol.h"
+#include "shap_tables.h"
 
 namespace {
 
@@ -125,6 +128,7 @@ Quantized quantize(const float* X, int n, int F) {
 struct Node {
   int feature = -1, split_bin = -1, left = -1, right = -1;
   double value = 0.0;
+  double cover = 0.0, gain = 0.0;   // hessian sum of the node's (sampled) rows; loss change of its split, 0 for leaves
 };
 
 struct GH { double g, h; };
@@ -177,6 +181,7 @@ Tree build_tree(const Quantized& q, const std::vector<GH>& gh, std::vector<int>&
     for (Work& w : level) {
       Node& nd = tree.nodes[w.node];
       nd.value = calc_weight(p, w.G, w.H) * p.eta;
+      nd.cover = w.H;
       if (depth == max_depth || w.end - w.begin < 2) continue;
       const double parent_gain = calc_gain(p, w.G, w.H);
       SplitResult best;
@@ -204,6 +209,7 @@ Tree build_tree(const Quantized& q, const std::vector<GH>& gh, std::vector<int>&
       tree.nodes.emplace_back();
       Node& pn = tree.nodes[w.node];
       pn.feature = f; pn.split_bin = sb; pn.left = li; pn.right = li + 1;
+      pn.gain = best.gain;
       Work L, R;
       L.node = li; L.begin = w.begin; L.end = mid; L.G = best.GL; L.H = best.HL;
       R.node = li + 1; R.begin = mid; R.end = w.end; R.G = w.G - best.GL; R.H = w.H - best.HL;
@@ -353,7 +359,7 @@ struct Forest {
   std::vector<long long> offsets{0};
   std::vector<int> feature, split_bin, left;
   std::vector<float> threshold;
-  std::vector<double> value;
+  std::vector<double> value, cover, gain;
   void add(const Tree& t, const Quantized& q) {
     for (const Node& nd : t.nodes) {
       const bool leaf = nd.left < 0;
@@ -362,6 +368,8 @@ struct Forest {
       left.push_back(leaf ? -1 : nd.left);
       threshold.push_back(leaf ? 0.f : q.upper[nd.feature][nd.split_bin]);
       value.push_back(nd.value);
+      cover.push_back(nd.cover);
+      gain.push_back(leaf ? 0.0 : nd.gain);
     }
     offsets.push_back((long long)feature.size());
   }
@@ -480,6 +488,17 @@ int gbdt_forest_copy(const void* forest, long long* offsets, int* feature, float
   return 0;
 }
 
+// The node statistics of the same forest, in gbdt_forest_copy's node order: cover (the hessian sum of the rows
+// the engine had in the node) and gain (the loss change of the node's split, 0 for leaves).
+int gbdt_forest_stats(const void* forest, double* cover, double* gain) {
+  const Forest* f = static_cast<const Forest*>(forest);
+  const size_t N = f->feature.size();
+  if (N == 0) return 0;
+  std::memcpy(cover, f->cover.data(), sizeof(double) * N);
+  std::memcpy(gain, f->gain.data(), sizeof(double) * N);
+  return 0;
+}
+
 void gbdt_forest_free(void* forest) { delete static_cast<Forest*>(forest); }
 
 // Predict on raw float rows with a compact forest (tree t: round t / K, class t % K; the first ntrees trees).
@@ -510,6 +529,46 @@ int gbdt_predict(const float* X, int n, int F, const long long* offsets, const i
         while (feature[o + j] >= 0) j = !(row[feature[o + j]] > threshold[o + j]) ? left[o + j] : left[o + j] + 1;
         if (out_margin) out_margin[(size_t)i * K + t % K] += value[o + j];
         if (out_leaf) out_leaf[(size_t)i * ntrees + t] = j;
+      }
+    }
+  };
+  if (nthreads == 1) {
+    work(0, n);
+    return 0;
+  }
+  std::vector<std::thread> th;
+  for (int t = 0; t < nthreads; ++t)
+    th.emplace_back(work, (int)((long long)n * t / nthreads), (int)((long long)n * (t + 1) / nthreads));
+  for (auto& x : th) x.join();
+  return 0;
+}
+
+// SHAP contributions of raw float rows (csrc/gbdt/shap_tables.h has the definition and the shared arithmetic):
+// out [n][K][F + 1] fp64, the last column the bias. The forest checks of gbdt_predict plus the cover checks
+// (-2), at most 64 unique features on a path (-3). Rows are split over nthreads; every (row, class) is
+// computed by one thread in the header's order, so the result does not depend on the thread count.
+int gbdt_predict_contribs(const float* X, int n, int F, const long long* offsets, const int* feature,
+                          const float* threshold, const int* left, const double* value, const double* cover,
+                          int ntrees, int K, double base, int nthreads, double* out) {
+  if (n < 0 || F <= 0 || K <= 0 || ntrees < 0 || ntrees % K || cover == nullptr || out == nullptr) return -1;
+  ShapTables tb;
+  if (const int rc = shap_build(F, offsets, feature, threshold, left, value, cover, ntrees, K, base, tb)) return rc;
+  const int rounds = ntrees / K;
+  if (nthreads <= 0) nthreads = (int)std::max(1u, std::thread::hardware_concurrency());
+  nthreads = std::max(1, std::min(nthreads, n / 16));
+  auto work = [&](int i0, int i1) {
+    double w[kShapMaxPath + 1];
+    for (int i = i0; i < i1; ++i) {
+      const float* row = X + (size_t)i * F;
+      for (int c = 0; c < K; ++c) {
+        double* phi = out + ((size_t)i * K + c) * ((size_t)F + 1);
+        std::fill(phi, phi + F, 0.0);
+        phi[F] = tb.bias[c];
+        for (int l = tb.leaf_off[c * rounds]; l < tb.leaf_off[(c + 1) * rounds]; ++l) {
+          const ShapLeaf& lf = tb.leaves[l];
+          shap_leaf(tb.elems.data() + lf.e0, lf.m, lf.value, row, tb.inv.data(), w,
+                    [phi](int f, double term) { phi[f] += term; });
+        }
       }
     }
   };

@@ -37,6 +37,10 @@ int gbdt_predict(const float* X, int n, int F, const long long* offsets, const i
                  const int* left, const double* value, int ntrees, int K, double base, int nthreads,
                  double* out_margin, int* out_leaf);
 int gbdt_cuts(const float* X, int n, int F, int* nbins_out, float* upper_out);
+int gbdt_forest_stats(const void* forest, double* cover, double* gain);
+int gbdt_predict_contribs(const float* X, int n, int F, const long long* offsets, const int* feature,
+                          const float* threshold, const int* left, const double* value, const double* cover,
+                          int ntrees, int K, double base, int nthreads, double* out);
 }
 
 namespace {
@@ -186,6 +190,8 @@ void train_predict(const Data& d, const double* p, int obj, int ncls, int metric
   std::vector<float> thr(N);
   std::vector<double> val(N);
   gbdt_forest_copy(forest, off.data(), feat.data(), thr.data(), sbin.data(), left.data(), val.data());
+  std::vector<double> cover(N), gain(N);
+  check(gbdt_forest_stats(forest, cover.data(), gain.data()) == 0, "gbdt_forest_stats rc");
   gbdt_forest_free(forest);
   check(off[0] == 0 && off[T] == (long long)N, "forest offsets");
   if (p[2] == 0) check(N == T, "depth 0: one leaf per tree");
@@ -223,6 +229,44 @@ void train_predict(const Data& d, const double* p, int obj, int ncls, int metric
   check(gbdt_predict(odd.data(), 4, d.F, off.data(), feat.data(), thr.data(), left.data(), val.data(), int(T), K, base, 2,
                      mo.data(), nullptr) == 0, "gbdt_predict rc, odd rows");
   for (double v : mo) check(std::isfinite(v), "odd rows: finite margins");
+  // node statistics and SHAP contributions: they add up to the margin, whatever the thread count
+  double leaf_sum = std::fabs(base);
+  long long first_split = -1, first_split_tree = 0;
+  for (size_t t = 0; t < T; ++t)
+    for (long long j = off[t]; j < off[t + 1]; ++j) {
+      check(cover[j] > 0.0 && std::isfinite(cover[j]), "cover positive");
+      check(feat[j] >= 0 ? gain[j] > 0.0 : gain[j] == 0.0, "gain: positive at splits, 0 at leaves");
+      if (feat[j] < 0) { leaf_sum += std::fabs(val[j]); continue; }
+      const long long l = off[t] + left[j];
+      check(cover[j] >= cover[l] && cover[j] >= cover[l + 1], "children's covers below the parent's");
+      if (first_split < 0) { first_split = j; first_split_tree = (long long)t; }
+    }
+  const size_t W = size_t(d.F) + 1;
+  std::vector<double> c1(size_t(d.n) * K * W, -1.0), c4(c1.size(), -2.0), co(size_t(4) * K * W);
+  check(gbdt_predict_contribs(d.X.data(), d.n, d.F, off.data(), feat.data(), thr.data(), left.data(), val.data(),
+                              cover.data(), int(T), K, base, 1, c1.data()) == 0, "gbdt_predict_contribs rc");
+  check(gbdt_predict_contribs(d.X.data(), d.n, d.F, off.data(), feat.data(), thr.data(), left.data(), val.data(),
+                              cover.data(), int(T), K, base, 4, c4.data()) == 0, "gbdt_predict_contribs rc, 4 threads");
+  check(std::memcmp(c1.data(), c4.data(), sizeof(double) * c1.size()) == 0, "contribs do not depend on threads");
+  check(gbdt_predict_contribs(odd.data(), 4, d.F, off.data(), feat.data(), thr.data(), left.data(), val.data(),
+                              cover.data(), int(T), K, base, 2, co.data()) == 0, "gbdt_predict_contribs rc, odd rows");
+  ok = true;
+  for (int i = 0; i < d.n + 4; ++i)
+    for (int c = 0; c < K; ++c) {
+      const double* phi = i < d.n ? &c1[(size_t(i) * K + c) * W] : &co[(size_t(i - d.n) * K + c) * W];
+      double sum = 0.0;
+      for (size_t f = 0; f < W; ++f) sum += phi[f];
+      const double m = i < d.n ? m1[size_t(i) * K + c] : mo[size_t(i - d.n) * K + c];
+      ok = ok && std::fabs(sum - m) <= 1e-12 * leaf_sum;
+    }
+  check(ok, "contribs add up to the margin");
+  if (first_split >= 0) {              // a zero children's cover sum is a malformed forest
+    std::vector<double> bad(cover);
+    const long long l = off[first_split_tree] + left[first_split];
+    bad[l] = bad[l + 1] = 0.0;
+    check(gbdt_predict_contribs(d.X.data(), 4, d.F, off.data(), feat.data(), thr.data(), left.data(), val.data(),
+                                bad.data(), int(T), K, base, 1, co.data()) == -2, "zero cover sum: malformed forest");
+  }
 }
 
 }  // namespace

@@ -538,12 +538,15 @@ __global__ void __launch_bounds__(256) best_kernel(Geo geo, const SplitOut* __re
 }
 
 // ---- plan: leaves, gamma pruning, split table, children totals (grid folds) --
+// cover / gain (null unless a tree sink wants node statistics): heap-indexed like leaf, the node's hessian sum
+// and the gain of its kept split (0 for a leaf).
 __global__ void __launch_bounds__(256) plan_split_kernel(Geo geo, int depth, const LNode* __restrict__ cur,
                                                          const NodeBest* __restrict__ best,
                                                          const unsigned int* __restrict__ mx, int2* __restrict__ tree,
                                                          float* __restrict__ leaf, int2* __restrict__ splitv,
                                                          int2* __restrict__ cursor, LNode* __restrict__ nxt,
-                                                         DevParams p) {
+                                                         DevParams p, double* __restrict__ cover,
+                                                         double* __restrict__ gain) {
   const int k = blockIdx.x, L = 1 << depth;
   const int tsz = (2 << geo.max_depth) - 1;
   const double ig = ldexp(1.0, -fx_exp(mx[2 * k], geo.lg_n)), ih = ldexp(1.0, -fx_exp(mx[2 * k + 1], geo.lg_n));
@@ -558,6 +561,10 @@ __global__ void __launch_bounds__(256) plan_split_kernel(Geo geo, int depth, con
       if (depth < geo.max_depth && nd.count >= 2) {
         b = best[(size_t)k * geo.Lh + j];
         split = b.feature >= 0 && b.bin >= 0 && b.gain >= p.gamma && b.gain > 1e-12;
+      }
+      if (cover != nullptr) {
+        cover[(size_t)k * tsz + id] = (double)nd.H * ih;
+        gain[(size_t)k * tsz + id] = split ? b.gain : 0.0;
       }
     }
     splitv[(size_t)k * geo.Lmax + j] = split ? make_int2(b.feature, b.bin) : make_int2(-1, 0);
@@ -946,6 +953,9 @@ enum : unsigned {
 // (children of i: 2i + 1, 2i + 2); entries the walk from the root does not reach are stale.
 extern "C" typedef void (*gbdt_tree_fn)(void* user, int round, int cls, const int* tree_xy, const float* leaf,
                                         int tsz, int max_depth);
+// The sink of gbdt_train_hip_stats: also the heap-indexed fp64 node statistics (plan_split_kernel's cover / gain).
+extern "C" typedef void (*gbdt_tree_stats_fn)(void* user, int round, int cls, const int* tree_xy, const float* leaf,
+                                              const double* cover, const double* gain, int tsz, int max_depth);
 
 namespace {
 
@@ -1017,7 +1027,11 @@ int ensure_bins(const uint8_t* bins_h, int n, int Fs, long long cache_key) {
 struct CvRun {
   Params p; int objective, n_metrics; const int* metrics; u64 seed; Tracer tr;
   gbdt_tree_fn tree_sink = nullptr; void* tree_user = nullptr;   // fold 0's trees (gbdt_train_hip: the only fold)
+  gbdt_tree_stats_fn stats_sink = nullptr;                       // the tree sink that also takes cover / gain
   int2* h_tree = nullptr; float* h_leaf = nullptr;               // pinned [K][tsz], only with a tree sink
+  double *d_cover = nullptr, *d_gain = nullptr;                  // [nfold][tsz], only with a stats sink
+  double *h_cover = nullptr, *h_gain = nullptr;                  // pinned [K][tsz], only with a stats sink
+  bool any_sink() const { return tree_sink != nullptr || stats_sink != nullptr; }
   int n, F, Fs, nfold, K, D;
   int obj;                 // grad_kernel's code: 0 squared error, 1 reg:logistic, 2 binary, 3 multi-class
   bool hconst, want_auc;   // hconst: h = 1 for every row -> count histograms for the hessian (hist_kernel<true>)
@@ -1114,9 +1128,15 @@ struct CvRun {
     }
     HC(ws.alloc_pinned(h_up, keys_bytes + sizeof(int) * K * order_elems));
     HC(ws.alloc_pinned(h_met, sizeof(double) * met_elems));
-    if (tree_sink) {
+    if (any_sink()) {
       HC(ws.alloc_pinned(h_tree, sizeof(int2) * (size_t)K * tsz));
       HC(ws.alloc_pinned(h_leaf, sizeof(float) * (size_t)K * tsz));
+    }
+    if (stats_sink) {
+      HC(ws.alloc(d_cover, sizeof(double) * (size_t)nfold * tsz));
+      HC(ws.alloc(d_gain, sizeof(double) * (size_t)nfold * tsz));
+      HC(ws.alloc_pinned(h_cover, sizeof(double) * (size_t)K * tsz));
+      HC(ws.alloc_pinned(h_gain, sizeof(double) * (size_t)K * tsz));
     }
     HC(hipMemcpy(d_y, y_h, sizeof(float) * n, hipMemcpyHostToDevice));
     HC(hipMemcpy(d_fold, fold_h, sizeof(int) * n, hipMemcpyHostToDevice));
@@ -1201,7 +1221,7 @@ struct CvRun {
         HC(tr.emit(round, c, d, GT_BEST, d_best, sizeof(NodeBest) * (size_t)nfold * geo.Lh));
       }
       hipLaunchKernelGGL(plan_split_kernel, dim3(nfold), dim3(256), 0, 0, geo, d, cur, d_best, d_mx, d_tree, d_leaf,
-                         d_split, d_cur, nxt, dp);
+                         d_split, d_cur, nxt, dp, d_cover, d_gain);
       HC(tr.emit(round, c, d, GT_SPLITV, d_split, sizeof(int2) * (size_t)nfold * geo.Lmax));
       if (d < D) {
         hipLaunchKernelGGL(partition_kernel, dim3(pblocks, nfold), dim3(256), 0, 0, geo, d, d_binsT, d_nroot, cur,
@@ -1223,16 +1243,24 @@ struct CvRun {
   // With a tree sink: queue the copy of fold 0's tree of class c behind its kernels (the next tree overwrites
   // d_tree / d_leaf); read_metrics' blocking copy waits for it.
   int stash_tree(int c) {
-    if (!tree_sink) return 0;
+    if (!any_sink()) return 0;
     HC(hipMemcpyAsync(h_tree + (size_t)c * tsz, d_tree, sizeof(int2) * tsz, hipMemcpyDeviceToHost, 0));
     HC(hipMemcpyAsync(h_leaf + (size_t)c * tsz, d_leaf, sizeof(float) * tsz, hipMemcpyDeviceToHost, 0));
+    if (stats_sink) {
+      HC(hipMemcpyAsync(h_cover + (size_t)c * tsz, d_cover, sizeof(double) * tsz, hipMemcpyDeviceToHost, 0));
+      HC(hipMemcpyAsync(h_gain + (size_t)c * tsz, d_gain, sizeof(double) * tsz, hipMemcpyDeviceToHost, 0));
+    }
     return 0;
   }
   void hand_out_trees(int round) const {
-    if (!tree_sink) return;
-    for (int c = 0; c < K; ++c)
-      tree_sink(tree_user, round, c, reinterpret_cast<const int*>(h_tree + (size_t)c * tsz), h_leaf + (size_t)c * tsz,
-                tsz, D);
+    for (int c = 0; c < K && any_sink(); ++c) {
+      const int* txy = reinterpret_cast<const int*>(h_tree + (size_t)c * tsz);
+      if (stats_sink)
+        stats_sink(tree_user, round, c, txy, h_leaf + (size_t)c * tsz, h_cover + (size_t)c * tsz,
+                   h_gain + (size_t)c * tsz, tsz, D);
+      else
+        tree_sink(tree_user, round, c, txy, h_leaf + (size_t)c * tsz, tsz, D);
+    }
   }
 
   // The round's metric launches and its blocking copies: early stopping needs the test metric.
@@ -1281,11 +1309,13 @@ struct CvRun {
   }
 };
 
-// One CV call of either entry point. tree_sink / out_margin (fold 0's final fp32 margins [n][K]) may be null.
+// One CV call of any entry point. tree_sink, stats_sink (at most one of the two) and out_margin (fold 0's final
+// fp32 margins [n][K]) may be null.
 int run_cv(const uint8_t* bins_h, int Fs, const int* nbins_h, int n, int F, const float* y_h, const int* fold_h,
            int nfold, const double* P, int objective, int num_class, const int* metrics, int n_metrics,
            int num_boost_round, int early_stopping_rounds, unsigned long long seed, long long cache_key,
-           double* out_hist, Tracer tr, gbdt_tree_fn tree_sink, void* tree_user, float* out_margin) {
+           double* out_hist, Tracer tr, gbdt_tree_fn tree_sink, void* tree_user, float* out_margin,
+           gbdt_tree_stats_fn stats_sink = nullptr) {
   if (objective < OBJ_SQUARED || objective > OBJ_MULTI_SOFTPROB || n_metrics < 1 || Fs % 4 || Fs < F || n <= 0 ||
       nfold <= 0 || F <= 0)
     return -1;
@@ -1303,7 +1333,7 @@ int run_cv(const uint8_t* bins_h, int Fs, const int* nbins_h, int n, int F, cons
   CvRun r;
   std::memcpy(&r.p, P, sizeof(Params));
   r.objective = objective; r.metrics = metrics; r.n_metrics = n_metrics; r.seed = seed; r.want_auc = want_auc;
-  r.tr = tr; r.tree_sink = tree_sink; r.tree_user = tree_user;
+  r.tr = tr; r.tree_sink = tree_sink; r.tree_user = tree_user; r.stats_sink = stats_sink;
   r.shape(n, F, Fs, nfold, num_class, fold_h);
   if (int rc = ensure_bins(bins_h, n, Fs, cache_key)) return rc;
   r.d_bins = gbdt_cache::bins; r.d_binsT = gbdt_cache::binsT.bins;
@@ -1366,10 +1396,11 @@ int gbdt_cv_hip(const uint8_t* bins_h, int Fs, const int* nbins_h, int n, int F,
 // round is handed to sink as its heap tables; the host compacts them (there is no device forest buffer).
 // out_hist [num_boost_round][n_metrics]: the train metrics; out_margin (may be null): the final fp32 margins
 // [n][K]. -8: max_depth beyond GB_MAXD (cv clamps; a model that people keep must not). Returns the rounds.
-int gbdt_train_hip(int Fs, const int* nbins_h, int n, int F, const float* y_h, const double* P, int objective,
-                   int num_class, const int* metrics, int n_metrics, int num_boost_round, unsigned long long seed,
-                   long long cache_key, double* out_hist, gbdt_tree_fn sink, void* user, float* out_margin) {
-  if (sink == nullptr || n <= 0 || n_metrics < 1 || num_boost_round < 1) return -1;
+static int train_hip(int Fs, const int* nbins_h, int n, int F, const float* y_h, const double* P, int objective,
+                     int num_class, const int* metrics, int n_metrics, int num_boost_round, unsigned long long seed,
+                     long long cache_key, double* out_hist, gbdt_tree_fn sink, gbdt_tree_stats_fn stats_sink,
+                     void* user, float* out_margin) {
+  if ((sink == nullptr) == (stats_sink == nullptr) || n <= 0 || n_metrics < 1 || num_boost_round < 1) return -1;
   Params p;
   std::memcpy(&p, P, sizeof(Params));
   if (p.max_depth > GB_MAXD) return -8;
@@ -1377,10 +1408,27 @@ int gbdt_train_hip(int Fs, const int* nbins_h, int n, int F, const float* y_h, c
   std::vector<double> hist4((size_t)num_boost_round * n_metrics * 4, 0.0);
   const int rc = run_cv(nullptr, Fs, nbins_h, n, F, y_h, fold.data(), 1, P, objective, num_class, metrics, n_metrics,
                         num_boost_round, 0, seed, cache_key, hist4.data(), Tracer{nullptr, nullptr, 0, 0u}, sink, user,
-                        out_margin);
+                        out_margin, stats_sink);
   if (rc < 0) return rc;
   for (size_t i = 0; i < (size_t)num_boost_round * n_metrics; ++i) out_hist[i] = hist4[i * 4];
   return rc;
+}
+
+int gbdt_train_hip(int Fs, const int* nbins_h, int n, int F, const float* y_h, const double* P, int objective,
+                   int num_class, const int* metrics, int n_metrics, int num_boost_round, unsigned long long seed,
+                   long long cache_key, double* out_hist, gbdt_tree_fn sink, void* user, float* out_margin) {
+  return train_hip(Fs, nbins_h, n, F, y_h, P, objective, num_class, metrics, n_metrics, num_boost_round, seed,
+                   cache_key, out_hist, sink, nullptr, user, out_margin);
+}
+
+// gbdt_train_hip whose sink also receives every tree's node statistics: cover (the hessian sum of the node's
+// rows, (double)H * 2^-fx_exp of the tree's hessian scale) and gain (the kept split's gain, 0 for a leaf).
+int gbdt_train_hip_stats(int Fs, const int* nbins_h, int n, int F, const float* y_h, const double* P, int objective,
+                         int num_class, const int* metrics, int n_metrics, int num_boost_round,
+                         unsigned long long seed, long long cache_key, double* out_hist, gbdt_tree_stats_fn sink,
+                         void* user, float* out_margin) {
+  return train_hip(Fs, nbins_h, n, F, y_h, P, objective, num_class, metrics, n_metrics, num_boost_round, seed,
+                   cache_key, out_hist, nullptr, sink, user, out_margin);
 }
 
 // struct sizes and constants the trace's reader needs: sizeof LNode, Chunk, Red, SplitOut, NodeBest; GB_R,

@@ -192,6 +192,8 @@ def train(params, x, y, num_boost_round=10, seed=0, device=None, nthreads=0, ret
                       "left": np.zeros(nn, np.int32), "value": np.zeros(nn, np.float64)}
             lib.gbdt_forest_copy(handle, *[arrays[k].ctypes.data for k in ("tree_offsets", "feature", "threshold",
                                                                            "split_bin", "left", "value")])
+            arrays["cover"], arrays["gain"] = np.zeros(nn, np.float64), np.zeros(nn, np.float64)
+            lib.gbdt_forest_stats(handle, arrays["cover"].ctypes.data, arrays["gain"].ctypes.data)
         finally:
             lib.gbdt_forest_free(handle)
     history = {"train-{}".format(m): hist[:, j].tolist() for j, m in enumerate(metrics)}

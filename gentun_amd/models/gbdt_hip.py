@@ -236,6 +236,8 @@ def cv_trace(x, y, fold_of, nfold, parr, obj, num_class, marr, nrounds, esr, see
 PREDICT_CHUNK_ROWS = 1 << 18      # rows per upload of Booster.predict(device='cuda...'); tests lower it
 _TREE_SINK = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
                               ctypes.c_int, ctypes.c_int)
+_TREE_STATS_SINK = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
+                                    ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int)
 
 
 def device_cuts(key, nbins):
@@ -251,9 +253,10 @@ def device_cuts(key, nbins):
 
 
 def train(x, y, parr, obj, num_class, marr, nrounds, seed, hist, x_key=None, return_margin=False):
-    """``gbdt.train`` on the GPU: the cv loop with one fold and no test rows; every tree's heap tables come back
-    with the round's metric read-back and are compacted here to the Booster's level-order numbering, with
-    thresholds from the device quantiser's cuts. Returns ``(Booster arrays, margins or None)``."""
+    """``gbdt.train`` on the GPU: the cv loop with one fold and no test rows; every tree's heap tables (nodes,
+    leaf values, and the fp64 node statistics cover / gain) come back with the round's metric read-back and are
+    compacted here to the Booster's level-order numbering, with thresholds from the device quantiser's cuts.
+    Returns ``(Booster arrays, margins or None)``."""
     from .booster import compact_heap_tree
     if not supported(obj, marr, 1):
         raise ValueError("objective / metrics not supported by the GPU engine")
@@ -261,10 +264,11 @@ def train(x, y, parr, obj, num_class, marr, nrounds, seed, hist, x_key=None, ret
     if parr[2] > maxd:
         raise ValueError("max_depth {:g} is beyond the GPU engine's deepest tree ({}): train on the CPU "
                          "engine instead".format(parr[2], maxd))
-    f = _lib.hip().gbdt_train_hip
+    f = _lib.hip().gbdt_train_hip_stats
     c = ctypes
     f.argtypes = [c.c_int, c.c_void_p, c.c_int, c.c_int, c.c_void_p, c.c_void_p, c.c_int, c.c_int, c.c_void_p,
-                  c.c_int, c.c_int, c.c_ulonglong, c.c_longlong, c.c_void_p, _TREE_SINK, c.c_void_p, c.c_void_p]
+                  c.c_int, c.c_int, c.c_ulonglong, c.c_longlong, c.c_void_p, _TREE_STATS_SINK, c.c_void_p,
+                  c.c_void_p]
     f.restype = c.c_int
     xk = x if x_key is None else x_key
     y = np.ascontiguousarray(y.astype(np.float32))
@@ -274,12 +278,14 @@ def train(x, y, parr, obj, num_class, marr, nrounds, seed, hist, x_key=None, ret
     margin32 = np.zeros((n, K), np.float32) if return_margin else None
     trees = []
 
-    def sink(_user, _rnd, _cls, tree_p, leaf_p, tsz, max_depth):
+    def sink(_user, _rnd, _cls, tree_p, leaf_p, cover_p, gain_p, tsz, max_depth):
         txy = np.frombuffer(ctypes.string_at(tree_p, 8 * tsz), dtype="<i4").reshape(tsz, 2)
         leaf = np.frombuffer(ctypes.string_at(leaf_p, 4 * tsz), dtype="<f4")
-        trees.append(compact_heap_tree(txy, leaf, max_depth))
+        cover = np.frombuffer(ctypes.string_at(cover_p, 8 * tsz), dtype="<f8")
+        gain = np.frombuffer(ctypes.string_at(gain_p, 8 * tsz), dtype="<f8")
+        trees.append(compact_heap_tree(txy, leaf, max_depth, cover, gain))
 
-    cb = _TREE_SINK(sink)
+    cb = _TREE_STATS_SINK(sink)
     for attempt in (0, 1):
         del trees[:]
         nb, key, fs = quantize_device(x, force=attempt > 0, ident=xk)
@@ -291,8 +297,10 @@ def train(x, y, parr, obj, num_class, marr, nrounds, seed, hist, x_key=None, ret
     if rc < 0:
         raise RuntimeError("gbdt_train_hip failed ({})".format(rc))
     upper = device_cuts(key, nb)
-    offsets, feature, split_bin, left, value, threshold = [0], [], [], [], [], []
-    for (tf, tb, tl, tv) in trees:
+    offsets, feature, split_bin, left, value, threshold, cover, gain = [0], [], [], [], [], [], [], []
+    for (tf, tb, tl, tv, tc, tg) in trees:
+        cover += tc
+        gain += tg
         feature += tf
         split_bin += tb
         left += tl
@@ -300,7 +308,7 @@ def train(x, y, parr, obj, num_class, marr, nrounds, seed, hist, x_key=None, ret
         threshold += [float(upper[a][b]) if a >= 0 else 0.0 for a, b in zip(tf, tb)]
         offsets.append(len(feature))
     arrays = {"tree_offsets": offsets, "feature": feature, "threshold": threshold, "split_bin": split_bin,
-              "left": left, "value": value}
+              "left": left, "value": value, "cover": cover, "gain": gain}
     return arrays, (None if margin32 is None else margin32.astype(np.float64))
 
 
@@ -328,5 +336,47 @@ def predict(bst, x, ntrees, out_margin, out_leaf, timing=None):
            None if out_leaf is None else out_leaf.ctypes.data, ms.ctypes.data)
     if rc != 0:
         raise RuntimeError("gbdt_predict_hip failed ({})".format(rc))
+    if timing is not None:
+        timing[:] = ms.tolist()
+
+
+# ---- SHAP contributions (csrc/hip/gbdt_shap.hip) ------------------------------------------------------------
+def shap_limit():
+    """The most unique features on one root-to-leaf path that gbdt_shap.hip handles."""
+    f = _lib.hip().gbdt_shap_hip_limit
+    f.argtypes = []
+    f.restype = ctypes.c_int
+    return int(f())
+
+
+def shap_rows(n_features):
+    """Rows per block that gbdt_shap.hip stages in LDS for this width (0: rows are read from global memory)."""
+    f = _lib.hip().gbdt_shap_hip_rows
+    f.argtypes = [ctypes.c_int]
+    f.restype = ctypes.c_int
+    return int(f(int(n_features)))
+
+
+def predict_contribs(bst, x, ntrees, out, timing=None):
+    """SHAP contributions (fp64 ``[n, K, F + 1]``, the bias last) of ``x`` with the first ``ntrees`` trees of
+    ``bst`` on the GPU; bit-identical to the CPU predictor. ``timing``: a list that receives
+    ``[kernel ms, ms including transfers]``."""
+    f = _lib.hip().gbdt_shap_hip
+    c = ctypes
+    f.argtypes = [c.c_void_p, c.c_int, c.c_int, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p,
+                  c.c_void_p, c.c_int, c.c_int, c.c_double, c.c_int, c.c_void_p, c.c_void_p]
+    f.restype = c.c_int
+    ms = np.zeros(2, np.float64)
+    rc = f(x.ctypes.data, x.shape[0], x.shape[1], bst.tree_offsets.ctypes.data, bst.feature.ctypes.data,
+           bst.threshold.ctypes.data, bst.left.ctypes.data, bst.value.ctypes.data, bst.cover.ctypes.data, int(ntrees),
+           bst.K, bst.base_margin, int(PREDICT_CHUNK_ROWS), out.ctypes.data, ms.ctypes.data)
+    if rc == -2:
+        raise ValueError("malformed forest: a split out of bounds, or children's covers that are not finite and "
+                         ">= 0 with a positive sum")
+    if rc == -3:
+        raise ValueError("a path of this model has more than {} unique features, the limit of the GPU SHAP "
+                         "kernel: use the CPU predictor (device=None)".format(shap_limit()))
+    if rc != 0:
+        raise RuntimeError("gbdt_shap_hip failed ({})".format(rc))
     if timing is not None:
         timing[:] = ms.tolist()

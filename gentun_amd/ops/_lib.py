@@ -102,6 +102,12 @@ def gbdt():
         lib.gbdt_predict.restype = c.c_int
         lib.gbdt_predict.argtypes = [c.c_void_p, c.c_int, c.c_int, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p,
                                      c.c_void_p, c.c_int, c.c_int, c.c_double, c.c_int, c.c_void_p, c.c_void_p]
+        lib.gbdt_forest_stats.restype = c.c_int
+        lib.gbdt_forest_stats.argtypes = [c.c_void_p] * 3
+        lib.gbdt_predict_contribs.restype = c.c_int
+        lib.gbdt_predict_contribs.argtypes = [c.c_void_p, c.c_int, c.c_int, c.c_void_p, c.c_void_p, c.c_void_p,
+                                              c.c_void_p, c.c_void_p, c.c_void_p, c.c_int, c.c_int, c.c_double,
+                                              c.c_int, c.c_void_p]
         lib._typed = True
     return lib
 

@@ -13,6 +13,7 @@
 #   bash tools/gpu.sh ga                      long RR-GA search with checkpoints (GENS= CKPT= BUDGET= GA_ARGS=)
 #   bash tools/gpu.sh gbdt                    GBDT GPU tests, GA bench and kernel stats (POP= ROUNDS=)
 #   bash tools/gpu.sh gbdt-predict            Booster.predict: GPU forest predictor vs the CPU predictor (ROWS= FEATURES= TREES= DEPTH= THREADS=)
+#   bash tools/gpu.sh gbdt-shap               Booster.predict(pred_contribs=True): GPU SHAP kernel vs the CPU predictor (ROWS= FEATURES= TREES= DEPTH= THREADS=)
 #   bash tools/gpu.sh rehearse                2-rank torchrun bench on one GPU (gloo control plane)
 #   bash tools/gpu.sh secondary               bench lines: reference fold semantics, torch comparator
 #
@@ -142,6 +143,12 @@ gbdt-predict)
     --trees ${TREES:-500} --depth ${DEPTH:-6} --threads ${THREADS:-16} ${PREDICT_ARGS:-} \
     2>&1 | tail -3 | cut -c1-900          # the result line; the script's status is the bench's (pipefail)
   exit $? ;;
+gbdt-shap)
+  heartbeat
+  timeout -k 10 ${TIME:-560} python -u tools/bench_gbdt_shap.py --rows ${ROWS:-200000} --features ${FEATURES:-256} \
+    --trees ${TREES:-500} --depth ${DEPTH:-6} --threads ${THREADS:-16} ${SHAP_ARGS:-} \
+    2>&1 | tail -3 | cut -c1-900          # the result line; the script's status is the bench's (pipefail)
+  exit $? ;;
 rehearse)
   heartbeat
   GENTUN_DIST_BACKEND=gloo timeout -k 10 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node ${N:-2} \
@@ -163,5 +170,5 @@ secondary)
     cat gpurun_out/sec/torch.json
   fi ;;
 *)
-  sed -n 2,18p "$0"; exit 2 ;;
+  sed -n 2,19p "$0"; exit 2 ;;
 esac
