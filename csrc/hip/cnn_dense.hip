@@ -431,6 +431,65 @@ __global__ void __launch_bounds__(64) head_fwd_kernel(HeadArgs a) {
   }
 }
 
+// Prediction head (the fitted model, models/cnn_fitted.py): the logits and class probabilities of every
+// row instead of a loss against a label. No label, gather table or step state is read.
+struct HeadPredictArgs {
+  const float* plog;       // [G][Up/16][B][C] partial logits from dense_fwd (evaluation mode)
+  const float* b2;         // [G][C]
+  float* logits;           // [G][B][C]
+  float* proba;            // [G][B][C]
+  int G, B, Up, C;
+};
+
+// One 64-lane wave per (group, row). The reduction is head_fwd_kernel's, operation for operation (lane t
+// sums tiles t, t + 64, ...; the same xor tree; + b2), so the logits are the floats an evaluation of the
+// same activations scores; then the same max-subtracted expf softmax. Lane c writes class c.
+__global__ void __launch_bounds__(64) head_predict_kernel(HeadPredictArgs a) {
+  const int idx = blockIdx.x, lane = threadIdx.x;
+  const int g = idx / a.B, b = idx % a.B;
+  const int C = a.C, nt = a.Up / 16;
+  float acc[HEAD_MAXC];
+  const float* pl = a.plog + ((long)g * nt * a.B + b) * C;
+#pragma unroll
+  for (int c = 0; c < HEAD_MAXC; ++c) acc[c] = 0.f;
+  // every class load of a tile issued at once (clamped index, masked add), as in head_fwd_kernel
+  for (int t = lane; t < nt; t += 64) {
+    float v[HEAD_MAXC];
+#pragma unroll
+    for (int c = 0; c < HEAD_MAXC; ++c) v[c] = pl[(long)t * a.B * C + min(c, C - 1)];
+#pragma unroll
+    for (int c = 0; c < HEAD_MAXC; ++c) acc[c] += c < C ? v[c] : 0.f;
+  }
+#pragma unroll
+  for (int c = 0; c < HEAD_MAXC; ++c) {
+    if (c < C) {
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) acc[c] += __shfl_xor(acc[c], o);
+    }
+  }
+  // the xor tree leaves every lane with the same sums: all lanes run the (uniform) softmax
+  float logit[HEAD_MAXC], p[HEAD_MAXC];
+  float mx = -INFINITY;
+#pragma unroll
+  for (int c = 0; c < HEAD_MAXC; ++c) {
+    logit[c] = c < C ? acc[c] + a.b2[(long)g * C + min(c, C - 1)] : -INFINITY;
+    if (c < C) mx = fmaxf(mx, logit[c]);
+  }
+  float z = 0.f;
+#pragma unroll
+  for (int c = 0; c < HEAD_MAXC; ++c)
+    if (c < C) { p[c] = expf(logit[c] - mx); z += p[c]; }
+  float lo = 0.f, pr = 0.f;
+#pragma unroll
+  for (int c = 0; c < HEAD_MAXC; ++c)
+    if (c < C && c == lane) { lo = logit[c]; pr = p[c] / z; }
+  if (lane < C) {
+    const long o = ((long)g * a.B + b) * C + lane;
+    a.logits[o] = lo;
+    a.proba[o] = pr;
+  }
+}
+
 // (2) grid (ceil(Up/64), G): per 64-unit slice, dH = (dz W2^T) * scale * (h > 0),
 //     gb1 = sum_b dH, gW2 = h^T dz; block 0 also gb2 = sum_b dz.
 __global__ void __launch_bounds__(256) head_bwd_kernel(HeadArgs a) {
@@ -992,6 +1051,14 @@ int gt_head(const HeadArgs* a, hipStream_t stream) {
   return (int)hipGetLastError();
 }
 
+int gt_head_predict(const HeadPredictArgs* a, hipStream_t stream) {
+  if (a->C < 1 || a->C > HEAD_MAXC || a->G < 1 || a->B < 1) return -1;
+  if (a->Up < 16 || a->Up % 16) return -2;
+  if (!a->plog || !a->b2 || !a->logits || !a->proba) return -3;
+  hipLaunchKernelGGL(head_predict_kernel, dim3(a->G * a->B), dim3(64), 0, stream, *a);
+  return (int)hipGetLastError();
+}
+
 int gt_dense_dgrad(const DenseDgradArgs* a, hipStream_t stream) {
   if (a->Fp % 64 && a->Fp % 8) return -1;
   if (a->unpool_mask && (a->Cp % 8 || a->Hs % 2 || a->Ws % 2 || (long)(a->Hs / 2) * (a->Ws / 2) * a->Cp != a->Fp))
@@ -1034,6 +1101,7 @@ size_t gt_sizeof_adam_seg() { return sizeof(AdamSeg); }
 int gt_adam_block_elems() { return ADAM_BLK; }
 size_t gt_sizeof_dense_fwd_args() { return sizeof(DenseFwdArgs); }
 size_t gt_sizeof_head_args() { return sizeof(HeadArgs); }
+size_t gt_sizeof_head_predict_args() { return sizeof(HeadPredictArgs); }
 size_t gt_sizeof_dense_dgrad_args() { return sizeof(DenseDgradArgs); }
 size_t gt_sizeof_dense_wgrad_args() { return sizeof(DenseWgradAdamArgs); }
 

@@ -190,7 +190,20 @@ def cmd_cnn(args):
                  epochs=_ints(args.epochs), learning_rate=_floats(args.lr), batch_size=args.batch, loss=args.loss,
                  seed=args.seed, optimizer=args.optimizer, momentum=args.momentum, dtype=args.dtype,
                  reset=args.fold_reset, batching=args.batching, batch_norm=args.batch_norm)
-    return _run_search(args, GeneticCnnIndividual, x, y, extra, maximize=True)
+    out = _run_search(args, GeneticCnnIndividual, x, y, extra, maximize=True)
+    if out is not None and args.save_model:
+        print(json.dumps(save_cnn_model(args.save_model, x, y, out["best_genes"], extra, device=_device())))
+    return out
+
+
+def save_cnn_model(path, x, y, genes, extra, device=None):
+    """``--save-model`` of the ``cnn`` sub-command (rank 0): refit the fittest individual's genes on all rows
+    with the search's own settings and write the classifier (.npz). Returns the line that is printed."""
+    from .models.cnn import GeneticCnnModel
+    model = GeneticCnnModel(x, y, genes, device=device, **extra)
+    clf = model.fit()
+    clf.save(path)
+    return {"saved_model": path, "genes": clf.genes, "metrics": clf.metrics}
 
 
 def cmd_xgb(args):
@@ -275,6 +288,8 @@ def main(argv=None):
     c.add_argument("--momentum", type=float, default=0.9, help="SGD momentum")
     c.add_argument("--batch-norm", action="store_true",
                    help="conv -> BatchNorm -> ReLU in every node (not in the reference network; off by default)")
+    c.add_argument("--save-model", default=None, metavar="PATH",
+                   help="after the search, refit the fittest individual on all rows and write the classifier (.npz)")
     c.set_defaults(fn=cmd_cnn)
     x = sub.add_parser("xgb", help="GBDT (XGBoost-style) hyper-parameter search")
     _common(x)

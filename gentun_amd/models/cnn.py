@@ -65,7 +65,8 @@ class GeneticCnnModel(GentunModel):
                                       self.kernel_sizes, self.dense_units, self.dropout_probability, self.classes)
         self.fold_scores = []
         self.fold_metrics = None
-        self.jobs = []               # the trained job(s) of the last cross_validate (reset_weights)
+        self.jobs = []               # the trained job(s) of the last cross_validate / fit (reset_weights)
+        self.fitted = None           # the CnnClassifier of the last fit()
 
     # ------------------------------------------------------------ structure
     def build_model(self, genes, nodes, input_shape, kernels_per_layer, kernel_sizes, dense_units,
@@ -168,3 +169,33 @@ class GeneticCnnModel(GentunModel):
             results.append(job.finish())
         self.jobs = jobs
         return self.collect(results)
+
+    # ------------------------------------------------------------ the final model
+    def fit(self):
+        """Train this candidate on every row of ``x_train`` with the model's own ``TrainConfig`` and keep
+        the result as ``self.fitted``, a :class:`~gentun_amd.models.cnn_fitted.CnnClassifier`.
+
+        One group in one job whose fold is (all rows, all rows): the job's evaluation then reports the
+        training-set metrics in evaluation mode (``fitted.metrics``). The fold id is ``nfold``, one past
+        the cross-validation folds, so the initialisation, shuffle and dropout streams -- keyed by
+        (seed, genes, fold id) -- are deterministic and distinct from every CV fold. ``self.jobs`` holds
+        the job, so :meth:`reset_weights` acts on the fitted weights."""
+        import numpy as np
+        from .cnn_fitted import CnnClassifier
+        rows = np.arange(len(self.x_train))
+        job = _eng.make_job(self.backend, self.model, self.x_train, self.y_train, [(rows, rows)], self.cfg,
+                            self.device, fold_ids=[self.nfold])
+        job.launch()
+        res = job.finish()
+        self.jobs = [job]
+        metrics = {"loss": float(res["val_loss"][0]), "binary_accuracy": float(res["binary_accuracy"][0]),
+                   "categorical_accuracy": float(res["categorical_accuracy"][0]), "rows": int(len(rows))}
+        self.fitted = CnnClassifier.from_job(job, 0, metrics=metrics)
+        return self.fitted
+
+    def predict(self, x, **kwargs):
+        """``self.fitted.predict`` on this model's device unless ``device`` says otherwise."""
+        if self.fitted is None:
+            raise RuntimeError("GeneticCnnModel.predict before fit()")
+        kwargs.setdefault("device", self.device)
+        return self.fitted.predict(x, **kwargs)

@@ -1,0 +1,411 @@
+"""``CnnClassifier`` -- a fitted Genetic-CNN model, independent of any training job.
+
+What a search leaves behind for keeping: the decoded architecture, the few configuration values the
+forward pass needs and the trained parameters as host fp32 arrays in plain layouts (conv kernels OIHW,
+``dense1.w`` rows in NCHW-flatten order -- the torch executor's names and shapes without the group
+axis). It is written to / read from one ``.npz`` (``gentun-cnn/1``: a JSON header string plus the
+arrays, no pickle) and predicts on
+
+* the CPU, or any torch device with ``backend="torch"``: the stock-torch functional forward of
+  :meth:`gentun_amd.models.cnn_engine.TorchFoldJob._forward` in evaluation mode with one group;
+* an MI355X: :class:`HipPredictor`, the forward-only launches of the HIP executor's evaluation
+  (:meth:`gentun_amd.models.cnn_hip.HipPopJob._build_eval_ops`) over a staging tensor of ``EB`` images,
+  ending in ``gt_head_predict`` (csrc/hip/cnn_dense.hip), which writes logits and probabilities instead
+  of a loss against a label.
+
+``GeneticCnnModel.fit()`` (models/cnn.py) trains a candidate on every row and returns one of these.
+"""
+
+import json
+
+import numpy as np
+import torch
+import torch.nn.functional as F
+
+from .genome import ConvSpec, make_plan
+
+FORMAT = "gentun-cnn/1"
+OUTPUTS = ("proba", "logits", "label")
+_BN_KINDS = ("gamma", "beta", "running_mean", "running_var")
+
+
+def predict_batch(batch):
+    """Rows per launch of the HIP predictor: ``batch`` rounded up to a multiple of 32, at least 32 and
+    at most 256 (the cap of ``HipPopJob.eval_batch``)."""
+    return max(32, min(256, (int(batch) + 31) // 32 * 32))
+
+
+class CnnClassifier(object):
+
+    def __init__(self, genes, nodes, input_shape, kernels_per_layer, kernel_sizes, dense_units, classes, params,
+                 batch_norm=False, bn_eps=1e-3, loss="bce_compat", dtype="fp32", metrics=None):
+        self.genes = dict(genes)
+        self.nodes = tuple(int(v) for v in nodes)
+        self.input_shape = tuple(int(v) for v in input_shape)
+        self.kernels_per_layer = tuple(int(v) for v in kernels_per_layer)
+        self.kernel_sizes = tuple(tuple(int(v) for v in k) for k in kernel_sizes)
+        self.dense_units = int(dense_units)
+        self.classes = int(classes)
+        self.batch_norm = bool(batch_norm)
+        self.bn_eps = float(bn_eps)
+        self.loss = loss
+        self.dtype = dtype
+        self.metrics = dict(metrics or {})
+        self.plan = make_plan(self.genes, self.nodes, self.input_shape, self.kernels_per_layer, self.kernel_sizes,
+                              self.dense_units, self.classes)
+        self.params = {}
+        for name, shape in self.param_shapes():
+            if name not in params:
+                raise ValueError("missing parameter {!r}".format(name))
+            a = np.ascontiguousarray(params[name], dtype=np.float32)
+            if a.shape != shape:
+                raise ValueError("parameter {!r} has shape {}, expected {}".format(name, a.shape, shape))
+            self.params[name] = a
+        self._torch_params = {}      # (device, dtype) -> {name: tensor}
+        self._predictors = {}        # (device, EB) -> HipPredictor
+
+    # ------------------------------------------------------------ structure
+    def param_shapes(self):
+        """``[(name, shape)]`` in the torch executor's order (cnn_engine.TorchFoldJob) without the group axis."""
+        p, out = self.plan, []
+        for st in p.convs():
+            out.append((st.name + ".w", (st.cout, st.cin, st.k[0], st.k[1])))
+            out.append((st.name + ".b", (st.cout,)))
+            if self.batch_norm:
+                out += [(st.name + "." + kind, (st.cout,)) for kind in _BN_KINDS]
+        out.append(("dense1.w", (p.flatten, p.dense_units)))
+        out.append(("dense1.b", (p.dense_units,)))
+        out.append(("dense2.w", (p.dense_units, p.classes)))
+        out.append(("dense2.b", (p.classes,)))
+        return out
+
+    def header(self):
+        return {"format": FORMAT, "genes": self.genes, "nodes": list(self.nodes),
+                "input_shape": list(self.input_shape), "kernels_per_layer": list(self.kernels_per_layer),
+                "kernel_sizes": [list(k) for k in self.kernel_sizes], "dense_units": self.dense_units,
+                "classes": self.classes, "batch_norm": self.batch_norm, "bn_eps": self.bn_eps, "loss": self.loss,
+                "dtype": self.dtype, "metrics": self.metrics}
+
+    # ------------------------------------------------------------ export / import
+    @classmethod
+    def from_job(cls, job, group=0, metrics=None):
+        """The parameters of group ``group`` of a live job (either executor) as a classifier."""
+        plan, cfg = job.members[job.gmember[group]][0], job.cfg
+        params = _export_hip(job, plan, group) if hasattr(job, "stage_cp") else _export_torch(job, group)
+        return cls(plan.genes, plan.nodes, plan.input_shape, plan.kernels_per_layer, plan.kernel_sizes,
+                   plan.dense_units, plan.classes, params, batch_norm=cfg.batch_norm, bn_eps=cfg.bn_eps,
+                   loss=cfg.loss, dtype=cfg.dtype, metrics=metrics)
+
+    def load_into(self, job, group=0):
+        """Write the parameters into group ``group`` of a job of this architecture (the inverse of
+        :meth:`from_job`). A HIP job gets the real extent of its padded masters, every padding element
+        zero, and its derived weight planes rebuilt."""
+        plan = job.members[job.gmember[group]][0]
+        if plan.key() != self.plan.key() or bool(job.cfg.batch_norm) != self.batch_norm:
+            raise ValueError("the job trains another architecture than this classifier's")
+        if hasattr(job, "stage_cp"):
+            _import_hip(self, job, group)
+        else:
+            _import_torch(self, job, group)
+
+    # ------------------------------------------------------------ file format
+    def save(self, path):
+        """One ``.npz``: the JSON header string plus one array per parameter."""
+        with open(path, "wb") as f:
+            np.savez(f, header=np.array(json.dumps(self.header())), **self.params)
+
+    @classmethod
+    def load(cls, path):
+        with np.load(path, allow_pickle=False) as z:
+            if "header" not in z.files:
+                raise ValueError("{}: not a {} file".format(path, FORMAT))
+            header = json.loads(str(z["header"][()]))
+            if header.get("format") != FORMAT:
+                raise ValueError("{}: format {!r}, expected {!r}".format(path, header.get("format"), FORMAT))
+            params = {name: z[name] for name in z.files if name != "header"}
+        return cls(header["genes"], header["nodes"], header["input_shape"], header["kernels_per_layer"],
+                   header["kernel_sizes"], header["dense_units"], header["classes"], params,
+                   batch_norm=header["batch_norm"], bn_eps=header["bn_eps"], loss=header["loss"],
+                   dtype=header["dtype"], metrics=header.get("metrics"))
+
+    # ------------------------------------------------------------ prediction
+    def _check_x(self, x):
+        x = np.asarray(x)
+        if x.ndim == 3:
+            x = x[None]
+        if x.ndim != 4 or tuple(x.shape[1:]) != self.input_shape:
+            raise ValueError("x must be [n, {}, {}, {}] (or one [H, W, C] image), got shape {}".format(
+                *(self.input_shape + (tuple(np.shape(x)),))))
+        return np.ascontiguousarray(x, dtype=np.float32)
+
+    def predict(self, x, device=None, output="proba", batch=256, backend=None, dtype=None):
+        """Class probabilities (``"proba"``: softmax, fp32 ``[n, classes]``), ``"logits"`` or ``"label"``
+        (int64: the most probable class, the lowest index on ties) of ``x`` ``[n, H, W, C]`` (or one
+        ``[H, W, C]`` image), ``batch`` rows at a time.
+
+        ``device`` None or ``"cpu"``: the stock-torch forward in fp32 (``dtype=torch.float64``: the
+        tests' oracle). A ``cuda`` device: the HIP predictor; ``backend="torch"`` the stock-torch forward
+        there instead. Both paths fill a short chunk with zero images (to ``EB`` rows on the HIP path,
+        to a multiple of 32 on the torch path) and return the real rows only, so a row's result does
+        not depend on how many rows are predicted with it."""
+        if output not in OUTPUTS:
+            raise ValueError("output {!r}: expected one of {}".format(output, OUTPUTS))
+        if int(batch) < 1:
+            raise ValueError("batch must be positive")
+        x = self._check_x(x)
+        dev = torch.device("cpu" if device is None else device)
+        if backend is None:
+            backend = "hip" if dev.type == "cuda" else "torch"
+        if backend == "hip":
+            if dtype is not None:
+                raise ValueError("dtype is an option of the torch backend")
+            logits, proba = self.hip_predictor(dev, batch).run(x)
+        elif backend == "torch":
+            logits, proba = self._torch_predict(x, dev, int(batch), dtype or torch.float32)
+        else:
+            raise ValueError("unknown backend {!r}".format(backend))
+        if output == "logits":
+            return logits
+        if output == "proba":
+            return proba
+        return np.argmax(proba, axis=1).astype(np.int64)          # first maximum: the head kernels' scan
+
+    def predict_classes(self, x, **kw):
+        return self.predict(x, output="label", **kw)
+
+    def hip_predictor(self, device, batch=256):
+        """The cached :class:`HipPredictor` of (device, rows per launch)."""
+        dev = torch.device(device)
+        if dev.type == "cuda" and dev.index is None:
+            dev = torch.device("cuda", torch.cuda.current_device())
+        key = (str(dev), predict_batch(batch))
+        pred = self._predictors.get(key)
+        if pred is None:
+            pred = self._predictors[key] = HipPredictor(self, dev, key[1])
+        return pred
+
+    def _tensors(self, dev, dtype):
+        key = (str(dev), dtype)
+        P = self._torch_params.get(key)
+        if P is None:
+            P = self._torch_params[key] = {k: torch.from_numpy(v).to(device=dev, dtype=dtype)
+                                           for k, v in self.params.items()}
+        return P
+
+    def _torch_forward(self, xb, P):
+        """``xb`` [n, C, H, W] -> logits [n, classes]: TorchFoldJob._forward(train=False), one group."""
+        acts = {"input": xb}
+        for st in self.plan.steps:
+            if isinstance(st, ConvSpec):
+                inp = acts[st.inputs[0]]
+                for extra in st.inputs[1:]:
+                    inp = inp + acts[extra]
+                z = F.conv2d(inp, P[st.name + ".w"], P[st.name + ".b"], padding=(st.k[0] // 2, st.k[1] // 2))
+                if self.batch_norm:
+                    n = st.name
+                    xh = (z - P[n + ".running_mean"].view(1, -1, 1, 1)) * \
+                        torch.rsqrt(P[n + ".running_var"].view(1, -1, 1, 1) + self.bn_eps)
+                    z = xh * P[n + ".gamma"].view(1, -1, 1, 1) + P[n + ".beta"].view(1, -1, 1, 1)
+                acts[st.name] = F.relu(z)
+            else:
+                acts[st.name] = F.max_pool2d(acts[st.srcs[0]], 2, 2)
+        feat = acts[self.plan.steps[-1].name].reshape(1, xb.shape[0], -1)
+        h = F.relu(torch.baddbmm(P["dense1.b"][None, None, :], feat, P["dense1.w"][None]))
+        return torch.baddbmm(P["dense2.b"][None, None, :], h, P["dense2.w"][None])[0]
+
+    def _torch_predict(self, x, dev, batch, dtype):
+        P = self._tensors(dev, dtype)
+        n = x.shape[0]
+        h, w, c = self.input_shape
+        logits = np.empty((n, self.classes), np.float64 if dtype == torch.float64 else np.float32)
+        proba = np.empty_like(logits)
+        with torch.no_grad():
+            for s in range(0, n, batch):
+                # a fresh NCHW buffer: canonical strides (a permuted one-channel image keeps NHWC strides and
+                # the convolution then takes its channels-last path, with other rounding than the
+                # executor's), rows padded with zero images to a multiple of 32 like the HIP predictor's
+                # launches (the BLAS / convolution paths of a batch of a few rows round differently)
+                m = min(batch, n - s)
+                buf = np.zeros(((m + 31) // 32 * 32, c, h, w), np.float32)
+                buf[:m] = x[s:s + m].transpose(0, 3, 1, 2)
+                lg = self._torch_forward(torch.from_numpy(buf).to(device=dev, dtype=dtype), P)[:m]
+                if dtype not in (torch.float32, torch.float64):
+                    lg = lg.float()
+                logits[s:s + batch] = lg.cpu().numpy()
+                proba[s:s + batch] = torch.softmax(lg, dim=-1).cpu().numpy()
+        return logits, proba
+
+
+# ---------------------------------------------------------------------------
+# parameter layouts of the two executors
+# ---------------------------------------------------------------------------
+
+def _np(t):
+    return t.detach().float().cpu().numpy().copy()
+
+
+def _export_torch(job, g):
+    V = job._views()
+    out = {}
+    for name, _, _, _ in job.shapes:
+        out[name] = _np(V[name][g])
+    for name, run in job.bn_run.items():
+        out[name + ".running_mean"] = _np(run[0][g])
+        out[name + ".running_var"] = _np(run[1][g])
+    return out
+
+
+def _import_torch(clf, job, g):
+    with torch.no_grad():
+        V = job._views()
+        for name, _, _, _ in job.shapes:
+            V[name][g].copy_(torch.from_numpy(clf.params[name]))
+        for name, run in job.bn_run.items():
+            run[0][g].copy_(torch.from_numpy(clf.params[name + ".running_mean"]))
+            run[1][g].copy_(torch.from_numpy(clf.params[name + ".running_var"]))
+
+
+def _hip_dense_geometry(job, plan):
+    hs, ws = job.final_hw
+    hr, wr = job.final_hw_real
+    return hs, ws, hr, wr, job.final_cp, plan.kernels_per_layer[-1], plan.dense_units
+
+
+def _export_hip(job, plan, g):
+    """Strip the channel padding, the ``Up`` padding and the padded-pixel rows of ``W1`` from the HIP
+    executor's fp32 masters (conv kernels ``[Coutp][KH][KW][Cinp]``, ``W1`` ``[hs][ws][Cp][Up]``)."""
+    layers = {L.name: L for L in job.layers}
+    out = {}
+    for st in plan.convs():
+        L = layers[st.name]
+        out[st.name + ".w"] = _np(L.w[0][g][:L.cout, :, :, :L.cin].permute(0, 3, 1, 2))
+        out[st.name + ".b"] = _np(L.b[0][g][:L.cout])
+        if job.bn:
+            out[st.name + ".gamma"] = _np(L.gamma[0][g][:L.cout])
+            out[st.name + ".beta"] = _np(L.beta[0][g][:L.cout])
+            out[st.name + ".running_mean"] = _np(L.bn_run[0][g][:L.cout])
+            out[st.name + ".running_var"] = _np(L.bn_run[1][g][:L.cout])
+    hs, ws, hr, wr, cp, C, U = _hip_dense_geometry(job, plan)
+    W1 = job.views["W1"][0][g].view(hs, ws, cp, job.Up)[:hr, :wr, :C, :U]            # NHWC features
+    out["dense1.w"] = _np(W1.permute(2, 0, 1, 3).reshape(C * hr * wr, U))              # -> NCHW flatten
+    out["dense1.b"] = _np(job.views["b1"][0][g][:U])
+    out["dense2.w"] = _np(job.views["W2"][0][g][:U])
+    out["dense2.b"] = _np(job.views["b2"][0][g])
+    return out
+
+
+def _import_hip(clf, job, g):
+    plan, dev = clf.plan, job.device
+    layers = {L.name: L for L in job.layers}
+
+    def t(name):
+        return torch.from_numpy(clf.params[name]).to(dev)
+
+    for L in job.layers:                         # every element of the group, padding included, to its
+        L.w[0][g].zero_()                        # untrained value; layers the genome lacks stay there
+        L.b[0][g].zero_()
+        if job.bn:
+            L.gamma[0][g].zero_()
+            L.beta[0][g].zero_()
+            L.bn_run[0][g].zero_()
+            L.bn_run[1][g].fill_(1.0)
+    for st in plan.convs():
+        L = layers[st.name]
+        L.w[0][g][:L.cout, :, :, :L.cin].copy_(t(st.name + ".w").permute(0, 2, 3, 1))
+        L.b[0][g][:L.cout].copy_(t(st.name + ".b"))
+        if job.bn:
+            L.gamma[0][g][:L.cout].copy_(t(st.name + ".gamma"))
+            L.beta[0][g][:L.cout].copy_(t(st.name + ".beta"))
+            L.bn_run[0][g][:L.cout].copy_(t(st.name + ".running_mean"))
+            L.bn_run[1][g][:L.cout].copy_(t(st.name + ".running_var"))
+    hs, ws, hr, wr, cp, C, U = _hip_dense_geometry(job, plan)
+    for name in ("W1", "b1", "W2", "b2"):
+        job.views[name][0][g].zero_()
+    W1 = job.views["W1"][0][g].view(hs, ws, cp, job.Up)
+    W1[:hr, :wr, :C, :U].copy_(t("dense1.w").view(C, hr, wr, U).permute(1, 2, 0, 3))
+    job.views["b1"][0][g][:U].copy_(t("dense1.b"))
+    job.views["W2"][0][g][:U].copy_(t("dense2.w"))
+    job.views["b2"][0][g].copy_(t("dense2.b"))
+    job._refresh_copies()        # bf16 planes, fragment planes and Winograd planes from the masters
+
+
+# ---------------------------------------------------------------------------
+# HIP predictor
+# ---------------------------------------------------------------------------
+
+class HipPredictor(object):
+    """Forward-only HIP launches of one fitted model at ``EB`` rows per launch.
+
+    Hosted on a one-group ``HipPopJob`` built over a staging tensor of ``EB`` zero images in the
+    executor's dataset layout: the job supplies the padded geometry, the parameter buffers and the
+    evaluation launches (``_build_eval_ops``: batch ``EB``, running statistics, no pool masks) with the
+    gather table ``arange(EB)``; it is never initialised, trained or captured. Each chunk of the input
+    is written into the staging tensor (a short tail is filled with zero images) and
+    ``gt_head_predict`` ends the chain. Independent of the number of rows predicted, so one predictor
+    serves every ``predict`` call of its (device, ``EB``)."""
+
+    def __init__(self, clf, device, EB):
+        from ..ops import cnn_kernels as K
+        from . import cnn_engine as E
+        from .cnn_hip import HipPopJob
+        self.K, self.EB, self.device, self.classes = K, int(EB), torch.device(device), clf.classes
+        if self.EB % 32 or not 32 <= self.EB <= 256:
+            raise ValueError("rows per launch must be a multiple of 32 in [32, 256]")
+        h, w, c = clf.input_shape
+        cfg = E.TrainConfig(epochs=(1,), learning_rate=(0.0,), batch_size=32, dropout=0.0, loss=clf.loss,
+                            dtype=clf.dtype, use_graph=False, batch_norm=clf.batch_norm, bn_eps=clf.bn_eps)
+        rows = np.arange(self.EB)
+        x0 = np.zeros((self.EB, h, w, c), np.float32)
+        y0 = np.zeros((self.EB, clf.classes), np.float32)
+        cache = list(E._DATA_CACHE)              # the staging tensor is this predictor's alone: it neither
+        try:                                     # stays in the dataset cache nor evicts a training set
+            job = HipPopJob(clf.plan, x0, y0, [(rows, rows)], cfg, self.device, fold_ids=[0])
+        finally:
+            E._DATA_CACHE[:] = cache
+        self.job = job
+        self.stage = job.data.x                  # [EB][Hp][Wp][C8], fp32 (nhwc8f) or bf16 (nhwc8)
+        self.hwc = (h, w, c)
+        with torch.cuda.device(self.device):
+            clf.load_into(job, 0)
+            self.ops, self.df, _, self._keep = job._build_eval_ops(self.EB)
+            self.gather = torch.arange(self.EB, dtype=torch.int64, device=self.device)
+            for kind, b, _ in self.ops:
+                if kind == "conv" and b.gather:
+                    b.gather = self.gather.data_ptr()
+            self.logits = torch.empty((1, self.EB, clf.classes), dtype=torch.float32, device=self.device)
+            self.proba = torch.empty_like(self.logits)
+            hp = K.HeadPredictArgs()
+            hp.plog, hp.b2 = self.df.plog, job.views["b2"][0].data_ptr()
+            hp.logits, hp.proba = self.logits.data_ptr(), self.proba.data_ptr()
+            hp.G, hp.B, hp.Up, hp.C = 1, self.EB, job.Up, clf.classes
+            self.head = hp
+
+    def forward(self):
+        """The launches of one chunk on the current stream: staging tensor -> ``logits`` / ``proba``."""
+        job, K = self.job, self.K
+        s = job._stream()
+        job._run_fwd(s, self.ops)
+        K.check(job.L.gt_dense_fwd(self.df, s), "dense_fwd(predict)")
+        K.check(job.L.gt_head_predict(self.head, s), "head_predict")
+
+    def upload(self, chunk):
+        """``chunk`` [m <= EB, H, W, C] host fp32 into the staging tensor; rows past ``m`` become zero images."""
+        m = chunk.shape[0]
+        h, w, c = self.hwc
+        if m < self.EB:
+            self.stage[m:].zero_()
+        self.stage[:m, :h, :w, :c].copy_(torch.from_numpy(chunk).to(self.device))
+
+    def run(self, x):
+        """``x`` [n, H, W, C] host fp32 -> (logits, proba) host fp32 ``[n, classes]``."""
+        n, EB = x.shape[0], self.EB
+        logits = torch.empty((n, self.classes), dtype=torch.float32, device=self.device)
+        proba = torch.empty_like(logits)
+        with torch.cuda.device(self.device):
+            for s in range(0, n, EB):
+                m = min(EB, n - s)
+                self.upload(x[s:s + m])
+                self.forward()
+                logits[s:s + m].copy_(self.logits[0, :m])
+                proba[s:s + m].copy_(self.proba[0, :m])
+            return logits.cpu().numpy(), proba.cpu().numpy()

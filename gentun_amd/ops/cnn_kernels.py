@@ -158,6 +158,11 @@ class HeadArgs(C.Structure):
                 ("prec", I), ("valid", P), ("valid_norm", P), ("dHp", P)]
 
 
+class HeadPredictArgs(C.Structure):
+    """csrc/hip/cnn_dense.hip HeadPredictArgs: logits and probabilities of every row (gt_head_predict)."""
+    _fields_ = [("plog", P), ("b2", P), ("logits", P), ("proba", P), ("G", I), ("B", I), ("Up", I), ("C", I)]
+
+
 class DenseDgradArgs(C.Structure):
     _fields_ = [("dH", P), ("wt", P), ("dx", P), ("G", I), ("B", I), ("Fp", I), ("Up", I), ("prec", I),
                 ("wps", C.c_long), ("unpool_mask", P), ("unpool_x0", P), ("unpool_x1", P), ("unpool_sel", P),
@@ -264,6 +269,10 @@ def lib():
             fn = getattr(L, name)
             fn.argtypes = [C.POINTER(BnArgs), P]
             fn.restype = I
+        L.gt_head_predict.argtypes = [C.POINTER(HeadPredictArgs), P]
+        L.gt_head_predict.restype = I
+        L.gt_sizeof_head_predict_args.restype = C.c_size_t
+        assert L.gt_sizeof_head_predict_args() == C.sizeof(HeadPredictArgs), "HeadPredictArgs ABI mismatch"
         L.gt_adam_segments.argtypes = [C.POINTER(AdamArgs), I, P]
         L.gt_adam_segments.restype = I
         L.gt_step_begin.argtypes = [P, P]

@@ -14,6 +14,7 @@
 #   bash tools/gpu.sh gbdt                    GBDT GPU tests, GA bench and kernel stats (POP= ROUNDS=)
 #   bash tools/gpu.sh gbdt-predict            Booster.predict: GPU forest predictor vs the CPU predictor (ROWS= FEATURES= TREES= DEPTH= THREADS=)
 #   bash tools/gpu.sh gbdt-shap               Booster.predict(pred_contribs=True): GPU SHAP kernel vs the CPU predictor (ROWS= FEATURES= TREES= DEPTH= THREADS=)
+#   bash tools/gpu.sh cnn-predict             CnnClassifier.predict: HIP predictor at 32 / 256 rows per launch vs stock torch on the GPU (ROWS= REPS=)
 #   bash tools/gpu.sh rehearse                2-rank torchrun bench on one GPU (gloo control plane)
 #   bash tools/gpu.sh secondary               bench lines: reference fold semantics, torch comparator
 #
@@ -149,6 +150,10 @@ gbdt-shap)
     --trees ${TREES:-500} --depth ${DEPTH:-6} --threads ${THREADS:-16} ${SHAP_ARGS:-} \
     2>&1 | tail -3 | cut -c1-900          # the result line; the script's status is the bench's (pipefail)
   exit $? ;;
+cnn-predict)
+  timeout -k 10 ${TIME:-420} python -u tools/bench_cnn_predict.py --rows ${ROWS:-10000} --reps ${REPS:-5} ${PREDICT_ARGS:-} \
+    2>&1 | tail -3 | cut -c1-2400         # the result line; the script's status is the bench's (pipefail)
+  exit $? ;;
 rehearse)
   heartbeat
   GENTUN_DIST_BACKEND=gloo timeout -k 10 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node ${N:-2} \
@@ -170,5 +175,5 @@ secondary)
     cat gpurun_out/sec/torch.json
   fi ;;
 *)
-  sed -n 2,19p "$0"; exit 2 ;;
+  sed -n 2,20p "$0"; exit 2 ;;
 esac
