@@ -22,7 +22,8 @@
 // gbdt_train fits the final model with the same tree-growing step (one fold, no test rows) and hands out its
 // trees with float thresholds and their node statistics (cover, gain: gbdt_forest_stats); gbdt_predict scores
 // raw rows with them, gbdt_predict_contribs explains them (shap_tables.h, shared with csrc/hip/gbdt_shap.hip;
-// gentun_amd/models/booster.py).
+// gentun_amd/models/booster.py), gbdt_predict_interactions by pairs of features (shap_interactions.h, shared
+// with csrc/hip/gbdt_shap_inter.hip).
 
 #include <algorithm>
 #include <atomic>
@@ -36,6 +37,7 @@
 
 #include "cv_protocol.h"
 #include "shap_tables.h"
+#include "shap_interactions.h"
 
 namespace {
 
@@ -569,6 +571,53 @@ int gbdt_predict_contribs(const float* X, int n, int F, const long long* offsets
           shap_leaf(tb.elems.data() + lf.e0, lf.m, lf.value, row, tb.inv.data(), w,
                     [phi](int f, double term) { phi[f] += term; });
         }
+      }
+    }
+  };
+  if (nthreads == 1) {
+    work(0, n);
+    return 0;
+  }
+  std::vector<std::thread> th;
+  for (int t = 0; t < nthreads; ++t)
+    th.emplace_back(work, (int)((long long)n * t / nthreads), (int)((long long)n * (t + 1) / nthreads));
+  for (auto& x : th) x.join();
+  return 0;
+}
+
+// SHAP interaction values of raw float rows (csrc/gbdt/shap_interactions.h has the definition and the shared
+// arithmetic): out [n][K][F + 1][F + 1] fp64. Arguments, checks and return codes of gbdt_predict_contribs. A
+// (row, class) matrix is accumulated in place by one thread in the header's order -- phi_i on the diagonal, the
+// pairs off it -- and finished there, so the result does not depend on the thread count.
+int gbdt_predict_interactions(const float* X, int n, int F, const long long* offsets, const int* feature,
+                              const float* threshold, const int* left, const double* value, const double* cover,
+                              int ntrees, int K, double base, int nthreads, double* out) {
+  if (n < 0 || F <= 0 || K <= 0 || ntrees < 0 || ntrees % K || cover == nullptr || out == nullptr) return -1;
+  ShapTables tb;
+  if (const int rc = shap_build(F, offsets, feature, threshold, left, value, cover, ntrees, K, base, tb)) return rc;
+  const int rounds = ntrees / K;
+  if (nthreads <= 0) nthreads = (int)std::max(1u, std::thread::hardware_concurrency());
+  nthreads = std::max(1, std::min(nthreads, n / 4));
+  const size_t F1 = (size_t)F + 1;
+  auto work = [&](int i0, int i1) {
+    double w[kShapMaxPath + 1], w2[kShapMaxPath];
+    for (int i = i0; i < i1; ++i) {
+      const float* row = X + (size_t)i * F;
+      for (int c = 0; c < K; ++c) {
+        double* phi = out + ((size_t)i * K + c) * F1 * F1;
+        std::fill(phi, phi + F1 * F1, 0.0);
+        for (int l = tb.leaf_off[c * rounds]; l < tb.leaf_off[(c + 1) * rounds]; ++l) {
+          const ShapLeaf& lf = tb.leaves[l];
+          shap_leaf_interactions(tb.elems.data() + lf.e0, lf.m, lf.value, row, tb.inv.data(), w, w2,
+                                 [](int) { return true; },
+                                 [phi, F1](int f, double term) { phi[(size_t)f * F1 + f] += term; },
+                                 [phi, F1](int a, int b, double term) { phi[(size_t)a * F1 + b] += term; });
+        }
+        for (int f = 0; f < F; ++f) {
+          const double* r = phi + (size_t)f * F1;
+          phi[(size_t)f * F1 + f] = shap_interaction_diagonal(F, f, [r](int j) { return r[j]; });
+        }
+        phi[F1 * F1 - 1] = tb.bias[c];
       }
     }
   };

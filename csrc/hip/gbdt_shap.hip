@@ -36,20 +36,16 @@
 #include <vector>
 
 #include "../gbdt/shap_tables.h"
+#include "gbdt_shap_host.h"
 
 namespace {
 
 using gbdt::ShapElem;
 using gbdt::ShapLeaf;
+using shap_host::Buffers;
+using shap_host::SChunk;
 
-#define SH_LDS_TOTAL (160 * 1024)   // gfx950: LDS per CU
-#define SH_TABLE_BYTES (32 * 1024)  // table chunk
-#define SH_MAXM 16                  // unique features on a path
 #define SH_T 256
-
-static_assert(sizeof(ShapElem) == 32 && sizeof(ShapLeaf) == 16, "table records are staged as 8-byte words");
-
-struct SChunk { int leaf0, nleaf, elem0, nelem, lds; };   // leaves / elements of consecutive trees of one class
 
 struct WeightColumn {               // w[k] of this thread: LDS [k][thread]
   double* p; int stride;
@@ -144,23 +140,6 @@ __global__ void __launch_bounds__(256) shap_transpose_kernel(const double* __res
   }
 }
 
-struct Buffers {
-  std::vector<void*> dev;
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  template <class T> hipError_t alloc(T*& p, size_t bytes) {
-    const hipError_t e = hipMalloc(&p, std::max<size_t>(bytes, 4));
-    if (e == hipSuccess) dev.push_back(p);
-    return e;
-  }
-  Buffers() = default; Buffers(const Buffers&) = delete;
-  ~Buffers() {
-    for (void* p : dev) (void)hipFree(p);
-    for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
-  }
-};
-
-#define SHC(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return -100 - (int)e_; } while (0)
-
 }  // namespace
 
 extern "C" {
@@ -190,35 +169,9 @@ int gbdt_shap_hip(const float* X_h, int n, int F, const long long* offsets, cons
   gbdt::ShapTables tb;
   if (const int rc = gbdt::shap_build(F, offsets, feature, threshold, left, value, cover, ntrees, K, base, tb)) return rc;
   if (tb.max_m > SH_MAXM) return -3;
-  const int rounds = ntrees / K;
-  // first element of every tree of the class-major list (a tree's leaves and elements are consecutive)
-  std::vector<int> tree_e0(ntrees + 1, (int)tb.elems.size());
-  for (int u = ntrees - 1; u >= 0; --u)
-    tree_e0[u] = tb.leaf_off[u] < tb.leaf_off[u + 1] ? tb.leaves[tb.leaf_off[u]].e0 : tree_e0[u + 1];
   std::vector<SChunk> chunks;
-  std::vector<int> cstart(K + 1, 0);
-  for (int c = 0; c < K; ++c) {
-    cstart[c] = (int)chunks.size();
-    SChunk cur{tb.leaf_off[c * rounds], 0, tree_e0[c * rounds], 0, 1};
-    for (int u = c * rounds; u < (c + 1) * rounds; ++u) {
-      const int nl = tb.leaf_off[u + 1] - tb.leaf_off[u], ne = tree_e0[u + 1] - tree_e0[u];
-      const size_t bytes = (size_t)nl * sizeof(ShapLeaf) + (size_t)ne * sizeof(ShapElem);
-      const bool big = bytes > SH_TABLE_BYTES;
-      const size_t have = (size_t)cur.nleaf * sizeof(ShapLeaf) + (size_t)cur.nelem * sizeof(ShapElem);
-      if (cur.nleaf > 0 && (big || have + bytes > SH_TABLE_BYTES)) {
-        chunks.push_back(cur);
-        cur = SChunk{tb.leaf_off[u], 0, tree_e0[u], 0, 1};
-      }
-      cur.nleaf += nl; cur.nelem += ne;
-      if (big) {                       // alone in its chunk, read from global memory
-        cur.lds = 0;
-        chunks.push_back(cur);
-        cur = SChunk{tb.leaf_off[u + 1], 0, tree_e0[u + 1], 0, 1};
-      }
-    }
-    if (cur.nleaf > 0) chunks.push_back(cur);
-  }
-  cstart[K] = (int)chunks.size();
+  std::vector<int> cstart;
+  shap_host::shap_chunks(tb, ntrees, K, SH_TABLE_BYTES, chunks, cstart);
 
   const int R = gbdt_shap_hip_rows(F), T = SH_T;
   const size_t lds = (size_t)SH_TABLE_BYTES + (size_t)(SH_MAXM + 1) * 8 * T + (R > 0 ? (size_t)R * (F + 1) * 4 : 0);

@@ -34,3 +34,9 @@ if __name__ == "__main__":
     bst.save(path)
     assert Booster.load(path).predict(x_test).tobytes() == pred.tobytes()
     print("saved", path)
+    # which two features the model uses together: SHAP interaction values, mean |Phi[i][j]| over the held-out rows
+    F = x_test.shape[1]
+    pair = np.abs(bst.predict(x_test, pred_interactions=True)[:, :F, :F]).mean(axis=0)
+    np.fill_diagonal(pair, 0.0)
+    i, j = np.unravel_index(int(np.argmax(pair)), pair.shape)
+    print("strongest interaction: features", int(min(i, j)), "and", int(max(i, j)), "mean |Phi|", float(pair[i, j]))

@@ -24,6 +24,11 @@ therefore bit-identical. Output transforms run on the host from the margins.
 csrc/gbdt/shap_tables.h defines; both predictors (``gbdt_predict_contribs``, csrc/hip/gbdt_shap.hip) run that
 header's arithmetic in its order and are bit-identical too. ``get_score`` is host-only numpy. A model saved
 before the node statistics existed loads with ``cover is None`` and raises where they are needed.
+
+``predict(pred_interactions=True)`` are SHAP interaction values under the same value function
+(csrc/gbdt/shap_interactions.h): ``[F + 1, F + 1]`` per row and class, symmetric, every row of the matrix adding
+up to the contribution, the bias in the last corner. ``gbdt_predict_interactions`` and
+csrc/hip/gbdt_shap_inter.hip are bit-identical as well.
 """
 
 import json
@@ -145,19 +150,47 @@ class Booster(object):
                 raise RuntimeError("gbdt_predict_contribs failed ({})".format(rc))
         return out[:, 0, :] if self.K == 1 else out
 
+    def _interactions(self, x, ntrees, device, nthreads):
+        self._need_stats()
+        n, F = x.shape
+        out = np.empty((n, self.K, F + 1, F + 1), np.float64)
+        if n > 0 and _is_gpu(device):
+            from . import gbdt_hip
+            gbdt_hip.predict_interactions(self, x, ntrees, out)
+        elif n > 0:
+            rc = _lib.gbdt().gbdt_predict_interactions(
+                x.ctypes.data, n, F, self.tree_offsets.ctypes.data, self.feature.ctypes.data,
+                self.threshold.ctypes.data, self.left.ctypes.data, self.value.ctypes.data, self.cover.ctypes.data,
+                ntrees, self.K, self.base_margin, int(nthreads), out.ctypes.data)
+            if rc == -2:
+                raise ValueError("malformed forest: a split out of bounds, or children's covers that are not "
+                                 "finite and >= 0 with a positive sum")
+            if rc == -3:
+                raise ValueError("a path with more than 64 unique features")
+            if rc != 0:
+                raise RuntimeError("gbdt_predict_interactions failed ({})".format(rc))
+        return out[:, 0] if self.K == 1 else out
+
     def predict(self, x, output_margin=False, pred_leaf=False, ntree_limit=0, device=None, nthreads=0,
-                pred_contribs=False):
+                pred_contribs=False, pred_interactions=False):
         """float64 predictions with xgboost's shapes: ``[n]`` (regression / binary, and the argmax class of
         ``multi:softmax``) or ``[n, K]`` (``multi:softprob``); ``output_margin`` the raw margins (``[n]`` or
         ``[n, K]``); ``pred_leaf`` int32 ``[n, T]`` tree-local leaf indices; ``pred_contribs`` float64 SHAP
         contributions to the margin, ``[n, F + 1]`` (``[n, K, F + 1]`` for K > 1) with the bias in the last
-        column; ``ntree_limit=k`` the first ``k`` rounds. ``device='cuda:0'`` runs the walk on the GPU."""
+        column; ``pred_interactions`` float64 SHAP interaction values, ``[n, F + 1, F + 1]``
+        (``[n, K, F + 1, F + 1]`` for K > 1), each matrix symmetric with rows that add up to the contributions
+        and the bias in the last corner; ``ntree_limit=k`` the first ``k`` rounds. ``device='cuda:0'`` runs the
+        walk on the GPU."""
         if pred_contribs and pred_leaf:
             raise ValueError("pred_contribs and pred_leaf exclude each other")
+        if pred_interactions and (pred_contribs or pred_leaf):
+            raise ValueError("pred_interactions excludes pred_contribs and pred_leaf")
         x = self._rows(x)
         ntrees = self._used_trees(ntree_limit)
         if pred_contribs:
             return self._contribs(x, ntrees, device, nthreads)
+        if pred_interactions:
+            return self._interactions(x, ntrees, device, nthreads)
         margin, leaf = self._raw(x, ntrees, bool(pred_leaf), device, nthreads)
         if pred_leaf:
             return leaf

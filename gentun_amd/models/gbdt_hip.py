@@ -380,3 +380,56 @@ def predict_contribs(bst, x, ntrees, out, timing=None):
         raise RuntimeError("gbdt_shap_hip failed ({})".format(rc))
     if timing is not None:
         timing[:] = ms.tolist()
+
+
+# ---- SHAP interaction values (csrc/hip/gbdt_shap_inter.hip) -------------------------------------------------
+def shap_inter_limit():
+    """The most unique features on one root-to-leaf path that gbdt_shap_inter.hip handles."""
+    f = _lib.hip().gbdt_shap_inter_hip_limit
+    f.argtypes = []
+    f.restype = ctypes.c_int
+    return int(f())
+
+
+def shap_inter_plan(n, n_features, num_class=1):
+    """``(rows per device chunk, feature-axis split S)`` of a ``predict_interactions`` call with these sizes, or
+    ``None`` when one row's output is beyond the kernel's per-buffer bound."""
+    f = _lib.hip().gbdt_shap_inter_hip_plan
+    f.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]
+    f.restype = ctypes.c_int
+    plan = np.zeros(2, np.int32)
+    rc = f(int(n), int(n_features), int(num_class), int(PREDICT_CHUNK_ROWS), plan.ctypes.data)
+    if rc == -4:
+        return None
+    if rc != 0:
+        raise ValueError("gbdt_shap_inter_hip_plan: bad sizes ({})".format(rc))
+    return int(plan[0]), int(plan[1])
+
+
+def predict_interactions(bst, x, ntrees, out, timing=None, split=0):
+    """SHAP interaction values (fp64 ``[n, K, F + 1, F + 1]``) of ``x`` with the first ``ntrees`` trees of ``bst``
+    on the GPU; bit-identical to the CPU predictor. ``timing``: a list that receives ``[kernel ms, ms including
+    transfers]``. ``split``: the kernel's feature-axis split, 0 = its own choice (the result does not depend on
+    it; tools compare the two)."""
+    f = _lib.hip().gbdt_shap_inter_hip_split
+    c = ctypes
+    f.argtypes = [c.c_void_p, c.c_int, c.c_int, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p,
+                  c.c_void_p, c.c_int, c.c_int, c.c_double, c.c_int, c.c_int, c.c_void_p, c.c_void_p]
+    f.restype = c.c_int
+    ms = np.zeros(2, np.float64)
+    rc = f(x.ctypes.data, x.shape[0], x.shape[1], bst.tree_offsets.ctypes.data, bst.feature.ctypes.data,
+           bst.threshold.ctypes.data, bst.left.ctypes.data, bst.value.ctypes.data, bst.cover.ctypes.data, int(ntrees),
+           bst.K, bst.base_margin, int(PREDICT_CHUNK_ROWS), int(split), out.ctypes.data, ms.ctypes.data)
+    if rc == -2:
+        raise ValueError("malformed forest: a split out of bounds, or children's covers that are not finite and "
+                         ">= 0 with a positive sum")
+    if rc == -3:
+        raise ValueError("a path of this model has more than {} unique features, the limit of the GPU SHAP "
+                         "interaction kernel: use the CPU predictor (device=None)".format(shap_inter_limit()))
+    if rc == -4:
+        raise ValueError("one row's interaction values ({} x {} x {} doubles) exceed the GPU kernel's 256 MB "
+                         "buffers: use the CPU predictor (device=None)".format(bst.K, x.shape[1] + 1, x.shape[1] + 1))
+    if rc != 0:
+        raise RuntimeError("gbdt_shap_inter_hip failed ({})".format(rc))
+    if timing is not None:
+        timing[:] = ms.tolist()

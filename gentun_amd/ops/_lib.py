@@ -108,6 +108,8 @@ def gbdt():
         lib.gbdt_predict_contribs.argtypes = [c.c_void_p, c.c_int, c.c_int, c.c_void_p, c.c_void_p, c.c_void_p,
                                               c.c_void_p, c.c_void_p, c.c_void_p, c.c_int, c.c_int, c.c_double,
                                               c.c_int, c.c_void_p]
+        lib.gbdt_predict_interactions.restype = c.c_int
+        lib.gbdt_predict_interactions.argtypes = lib.gbdt_predict_contribs.argtypes
         lib._typed = True
     return lib
 

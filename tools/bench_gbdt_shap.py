@@ -8,7 +8,12 @@ a leaf costs the same as in a trained forest of that shape. Reported: the GPU's 
 including the table build, the row upload and the read-back (best of ``--reps`` runs after a first call that
 loads the library), and the CPU predictor with ``--threads`` threads (best of ``--cpu-reps``).
 
+``--interactions`` measures Booster.predict(pred_interactions=True) instead (csrc/hip/gbdt_shap_inter.hip against
+gbdt_predict_interactions), in the same way; ``--splits 0,1,16`` then times the kernel with each feature-axis
+split in turn (0: its own choice), alternating them within every repetition, and compares every output.
+
 usage: python tools/bench_gbdt_shap.py [--rows 200000] [--features 256] [--trees 500] [--depth 6] [--threads 16]
+                                       [--interactions [--splits 0,1]]
 """
 import argparse
 import json
@@ -29,6 +34,8 @@ ap.add_argument("--classes", type=int, default=1)
 ap.add_argument("--threads", type=int, default=16)
 ap.add_argument("--reps", type=int, default=2)
 ap.add_argument("--cpu-reps", type=int, default=1, help="0: GPU timings only, nothing is compared")
+ap.add_argument("--interactions", action="store_true", help="pred_interactions instead of pred_contribs")
+ap.add_argument("--splits", default="0", help="with --interactions: feature-axis splits to time, 0 = the kernel's choice")
 args = ap.parse_args()
 
 from gentun_amd.models import gbdt_hip  # noqa: E402
@@ -55,6 +62,44 @@ bst = Booster(tree_offsets=np.arange(T + 1) * nn, feature=feature, threshold=thr
               split_bin=np.where(feature >= 0, 0, -1), left=left, value=0.01 * rng.standard_normal((T, nn)),
               objective=5 if args.classes > 1 else 0, num_class=args.classes, base_margin=0.5,
               n_features=args.features, params={}, history={}, cover=cover, gain=np.zeros((T, nn)))
+
+if args.interactions:
+    splits = [int(v) for v in args.splits.split(",")]
+    F1 = args.features + 1
+    outs = {sp: np.empty((args.rows, args.classes, F1, F1), np.float64) for sp in splits}
+    kernel_ms, total_ms = {sp: [] for sp in splits}, {sp: [] for sp in splits}
+    for _ in range(args.reps + 1):              # the first GPU run also loads the library and creates the context
+        for sp in splits:
+            ms = []
+            gbdt_hip.predict_interactions(bst, x, T, outs[sp], timing=ms, split=sp)
+            kernel_ms[sp].append(ms[0])
+            total_ms[sp].append(ms[1])
+    cpu_s, cpu = [], None
+    for _ in range(args.cpu_reps):
+        t0 = time.perf_counter()
+        cpu = bst.predict(x, pred_interactions=True, nthreads=args.threads)
+        cpu_s.append(time.perf_counter() - t0)
+    ref = cpu if cpu_s else outs[splits[0]]
+    same = all(o.reshape(ref.shape).tobytes() == ref.tobytes() for o in outs.values())
+    nm = min(1000, args.rows)
+    margin = bst.predict(x[:nm], output_margin=True).reshape(nm, args.classes)
+    additive = float(np.abs(outs[splits[0]][:nm].sum(axis=(2, 3)) - margin).max())
+    plan = gbdt_hip.shap_inter_plan(args.rows, args.features, args.classes)
+    best = splits[0]
+    print(json.dumps({"metric": "Booster.predict(pred_interactions=True), rows/s", "rows": args.rows,
+                      "features": args.features, "trees": args.trees, "depth": args.depth, "classes": args.classes,
+                      "chunk_rows": plan[0], "chosen_split": plan[1],
+                      "bytewise_equal_to_cpu" if cpu_s else "splits_bytewise_equal": same,
+                      "max_abs_sum_minus_margin_first_1000_rows": additive,
+                      "gpu_kernel_ms": round(min(kernel_ms[best][1:]), 3),
+                      "gpu_with_transfers_ms": round(min(total_ms[best][1:]), 3),
+                      "gpu_first_call_ms": round(total_ms[best][0], 3),
+                      "gpu_kernel_ms_by_split": {str(sp): [round(v, 3) for v in kernel_ms[sp][1:]] for sp in splits},
+                      "cpu_threads": args.threads, "cpu_ms": round(1e3 * min(cpu_s), 3) if cpu_s else None,
+                      "gpu_kernel_rows_per_s": round(args.rows / (1e-3 * min(kernel_ms[best][1:]))),
+                      "gpu_rows_per_s": round(args.rows / (1e-3 * min(total_ms[best][1:]))),
+                      "cpu_rows_per_s": round(args.rows / min(cpu_s)) if cpu_s else None}), flush=True)
+    sys.exit(0 if same else 1)
 
 gpu_total_ms, gpu_kernel_ms = [], []
 out = np.empty((args.rows, args.classes, args.features + 1), np.float64)

@@ -28,22 +28,23 @@ ARCH = os.environ.get("GENTUN_HIP_ARCH", "gfx950")
 TARGETS = {
     "libgentun_gbdt.so": {
         "sources": ["csrc/gbdt/engine.cpp"],
-        "deps": ["csrc/gbdt/cv_protocol.h", "csrc/gbdt/shap_tables.h"],
+        "deps": ["csrc/gbdt/cv_protocol.h", "csrc/gbdt/shap_tables.h", "csrc/gbdt/shap_interactions.h"],
         "kind": "cxx",
     },
     # host sanitizer build of the GBDT engine: ASan + UBSan,
     # loaded through GENTUN_GBDT_LIB by tests/test_sanitizers.py
     "libgentun_gbdt_asan.so": {
         "sources": ["csrc/gbdt/engine.cpp"],
-        "deps": ["csrc/gbdt/cv_protocol.h", "csrc/gbdt/shap_tables.h"],
+        "deps": ["csrc/gbdt/cv_protocol.h", "csrc/gbdt/shap_tables.h", "csrc/gbdt/shap_interactions.h"],
         "kind": "cxx_asan",
         "optional": True,
     },
     "libgentun_hip.so": {
         "sources": sorted(glob.glob(os.path.join(ROOT, "csrc", "hip", "*.hip"))),
-        # gbdt_hist.hip / gbdt_shap.hip include what they share with the CPU engine by relative path
-        "deps": sorted(glob.glob(os.path.join(ROOT, "csrc", "hip", "*.h"))) + ["csrc/gbdt/cv_protocol.h",
-                                                                                "csrc/gbdt/shap_tables.h"],
+        # gbdt_hist.hip / gbdt_shap.hip / gbdt_shap_inter.hip include what they share with the CPU engine by
+        # relative path
+        "deps": sorted(glob.glob(os.path.join(ROOT, "csrc", "hip", "*.h"))) + [
+            "csrc/gbdt/cv_protocol.h", "csrc/gbdt/shap_tables.h", "csrc/gbdt/shap_interactions.h"],
         "kind": "hip",
     },
 }

@@ -14,6 +14,7 @@
 #   bash tools/gpu.sh gbdt                    GBDT GPU tests, GA bench and kernel stats (POP= ROUNDS=)
 #   bash tools/gpu.sh gbdt-predict            Booster.predict: GPU forest predictor vs the CPU predictor (ROWS= FEATURES= TREES= DEPTH= THREADS=)
 #   bash tools/gpu.sh gbdt-shap               Booster.predict(pred_contribs=True): GPU SHAP kernel vs the CPU predictor (ROWS= FEATURES= TREES= DEPTH= THREADS=)
+#   bash tools/gpu.sh gbdt-interactions       Booster.predict(pred_interactions=True): GPU kernel vs the CPU predictor (ROWS= FEATURES= TREES= DEPTH= THREADS= SPLITS=)
 #   bash tools/gpu.sh cnn-predict             CnnClassifier.predict: HIP predictor at 32 / 256 rows per launch vs stock torch on the GPU (ROWS= REPS=)
 #   bash tools/gpu.sh rehearse                2-rank torchrun bench on one GPU (gloo control plane)
 #   bash tools/gpu.sh secondary               bench lines: reference fold semantics, torch comparator
@@ -150,6 +151,13 @@ gbdt-shap)
     --trees ${TREES:-500} --depth ${DEPTH:-6} --threads ${THREADS:-16} ${SHAP_ARGS:-} \
     2>&1 | tail -3 | cut -c1-900          # the result line; the script's status is the bench's (pipefail)
   exit $? ;;
+gbdt-interactions)
+  heartbeat
+  timeout -k 10 ${TIME:-300} python -u tools/bench_gbdt_shap.py --interactions --rows ${ROWS:-20000} \
+    --features ${FEATURES:-32} --trees ${TREES:-500} --depth ${DEPTH:-6} --threads ${THREADS:-16} \
+    --splits ${SPLITS:-0} ${SHAP_ARGS:-} \
+    2>&1 | tail -3 | cut -c1-1200         # the result line; the script's status is the bench's (pipefail)
+  exit $? ;;
 cnn-predict)
   timeout -k 10 ${TIME:-420} python -u tools/bench_cnn_predict.py --rows ${ROWS:-10000} --reps ${REPS:-5} ${PREDICT_ARGS:-} \
     2>&1 | tail -3 | cut -c1-2400         # the result line; the script's status is the bench's (pipefail)
@@ -175,5 +183,5 @@ secondary)
     cat gpurun_out/sec/torch.json
   fi ;;
 *)
-  sed -n 2,20p "$0"; exit 2 ;;
+  sed -n 2,21p "$0"; exit 2 ;;
 esac
