@@ -1,5 +1,6 @@
 """BatchNorm kernels (csrc/hip/cnn_bn.hip) against torch.nn.BatchNorm2d:
-forward (batch and running statistics, fused ReLU), running-stat update,
+forward (batch and running statistics, fused ReLU), the saved mean / rstd
+against fp64 (tests/bn_ref.py), running-stat update,
 backward (dz, dgamma, dbeta), population group tables, the Keras short
 batch; and the deep S=(3,4,5) space learning at the reference lr 1e-3. The
 composed step with BatchNorm is checked gradient by gradient against fp64
@@ -8,6 +9,8 @@ autograd and over 50 steps against torch in tests/test_hip_step_parity.py."""
 import numpy as np
 import pytest
 import torch
+
+from bn_ref import bn_compare, bn_oracle
 
 pytestmark = pytest.mark.gpu
 
@@ -90,6 +93,13 @@ def test_bn_kernels_match_batchnorm2d(prec, shape):
         assert float(y[g, ..., C:].float().abs().max()) == 0.0          # padding channels stay 0
         assert _rel(run_d[0, g, :C], m.running_mean) < 1e-5
         assert _rel(run_d[1, g, :C], m.running_var) < 1e-5
+        # the saved statistics (fp32 in both precisions; the backward runs on them) against fp64, at the
+        # fp32 bound of tests/bn_ref.py: min(1e-4, max(1e-5, 8 x the error of stock torch fp32))
+        ref = bn_oracle(zf[g, ..., :C], gamma[g, :C], beta[g, :C], run[:, g, :C], nv, 0, 0, 1e-3, 0.99)
+        assert _rel(ref["y"][:nv], yref) < 1e-12
+        errs = bn_compare({"mean": stat[g, 0, :C], "rstd": stat[g, 1, :C]}, ref, prec)
+        print("[bn] {} prec {} group {} stat: mean {:.2e} rstd {:.2e} (torch-fp32 {:.2e} {:.2e})".format(
+            shape, prec, g, errs["mean"], errs["rstd"], ref["E_torch"]["mean"], ref["E_torch"]["rstd"]))
         out.backward(gy[g, :nv, ..., :C].permute(0, 3, 1, 2).double())
         dz = gbuf[g].float().cpu()
         assert _rel(dz[:nv, ..., :C], x.grad.permute(0, 2, 3, 1)) < tol, "dz"
