@@ -441,22 +441,20 @@ struct HeadPredictArgs {
   int G, B, Up, C;
 };
 
-// One 64-lane wave per (group, row). The reduction is head_fwd_kernel's, operation for operation (lane t
-// sums tiles t, t + 64, ...; the same xor tree; + b2), so the logits are the floats an evaluation of the
-// same activations scores; then the same max-subtracted expf softmax. Lane c writes class c.
-__global__ void __launch_bounds__(64) head_predict_kernel(HeadPredictArgs a) {
-  const int idx = blockIdx.x, lane = threadIdx.x;
-  const int g = idx / a.B, b = idx % a.B;
-  const int C = a.C, nt = a.Up / 16;
+// The logit and probability of class `lane` of one (group, row), computed by one 64-lane wave. The reduction
+// is head_fwd_kernel's, operation for operation (lane t sums tiles t, t + 64, ...; the same xor tree; + b2),
+// so the logits are the floats an evaluation of the same activations scores; then the same max-subtracted
+// expf softmax. `pl` points at the row's first tile, `b2` at the group's bias. Lanes >= C get zeros.
+__device__ __forceinline__ void head_row_softmax(const float* pl, const float* b2, int B, int C, int nt, int lane,
+                                                 float& lo, float& pr) {
   float acc[HEAD_MAXC];
-  const float* pl = a.plog + ((long)g * nt * a.B + b) * C;
 #pragma unroll
   for (int c = 0; c < HEAD_MAXC; ++c) acc[c] = 0.f;
   // every class load of a tile issued at once (clamped index, masked add), as in head_fwd_kernel
   for (int t = lane; t < nt; t += 64) {
     float v[HEAD_MAXC];
 #pragma unroll
-    for (int c = 0; c < HEAD_MAXC; ++c) v[c] = pl[(long)t * a.B * C + min(c, C - 1)];
+    for (int c = 0; c < HEAD_MAXC; ++c) v[c] = pl[(long)t * B * C + min(c, C - 1)];
 #pragma unroll
     for (int c = 0; c < HEAD_MAXC; ++c) acc[c] += c < C ? v[c] : 0.f;
   }
@@ -472,21 +470,94 @@ __global__ void __launch_bounds__(64) head_predict_kernel(HeadPredictArgs a) {
   float mx = -INFINITY;
 #pragma unroll
   for (int c = 0; c < HEAD_MAXC; ++c) {
-    logit[c] = c < C ? acc[c] + a.b2[(long)g * C + min(c, C - 1)] : -INFINITY;
+    logit[c] = c < C ? acc[c] + b2[min(c, C - 1)] : -INFINITY;
     if (c < C) mx = fmaxf(mx, logit[c]);
   }
   float z = 0.f;
 #pragma unroll
   for (int c = 0; c < HEAD_MAXC; ++c)
     if (c < C) { p[c] = expf(logit[c] - mx); z += p[c]; }
-  float lo = 0.f, pr = 0.f;
+  lo = 0.f; pr = 0.f;
 #pragma unroll
   for (int c = 0; c < HEAD_MAXC; ++c)
     if (c < C && c == lane) { lo = logit[c]; pr = p[c] / z; }
+}
+
+// One 64-lane wave per (group, row); lane c writes class c.
+__global__ void __launch_bounds__(64) head_predict_kernel(HeadPredictArgs a) {
+  const int idx = blockIdx.x, lane = threadIdx.x;
+  const int g = idx / a.B, b = idx % a.B;
+  const int C = a.C, nt = a.Up / 16;
+  float lo, pr;
+  head_row_softmax(a.plog + ((long)g * nt * a.B + b) * C, a.b2 + (long)g * C, a.B, C, nt, lane, lo, pr);
   if (lane < C) {
     const long o = ((long)g * a.B + b) * C + lane;
     a.logits[o] = lo;
     a.proba[o] = pr;
+  }
+}
+
+// Ensemble head (models/cnn_ensemble.py): ends the forward chain of a G-group predictor whose groups are
+// the members of an ensemble, and combines them on the device.
+struct HeadEnsembleArgs {
+  const float* plog;       // [G][Up/16][B][C] partial logits from dense_fwd (evaluation mode)
+  const float* b2;         // [G][C]
+  const float* weight;     // [G] fp32, normalised on the host
+  float* logits;           // [G][B][C], may be null
+  float* proba;            // [G][B][C], may be null
+  float* ens;              // [B][C]  weighted mean of the members' probabilities
+  int* votes;              // [B][C]  number of members whose most probable class is c
+  int G, B, Up, C;
+};
+
+#define ENS_MAXG 64
+
+// sum_g w[g] * ps[g][c] in member order, the multiply and the add rounded separately (what the host's
+// fp32 numpy combine does), so the pragma keeps the compiler from fusing them.
+__device__ __forceinline__ float ensemble_mean(const float* w, const float (*ps)[HEAD_MAXC], int G, int c) {
+#pragma clang fp contract(off)
+  float acc = w[0] * ps[0][c];
+  for (int g = 1; g < G; ++g) {
+    const float term = w[g] * ps[g][c];
+    acc = acc + term;
+  }
+  return acc;
+}
+
+// One workgroup of 4 waves per row b; wave w runs head_predict_kernel's wave for members w, w + 4, ... (the
+// same helper, so member g's logits and probabilities are the floats gt_head_predict writes for group g)
+// and leaves the probabilities and the member's vote (its first maximum) in LDS. After the barrier lanes
+// c < C of wave 0 combine the members in member order.
+__global__ void __launch_bounds__(256) head_ensemble_kernel(HeadEnsembleArgs a) {
+  __shared__ float ps[ENS_MAXG][HEAD_MAXC];
+  __shared__ int arg[ENS_MAXG];
+  const int b = blockIdx.x, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int C = a.C, nt = a.Up / 16;
+  for (int g = wave; g < a.G; g += 4) {
+    float lo, pr;
+    head_row_softmax(a.plog + ((long)g * nt * a.B + b) * C, a.b2 + (long)g * C, a.B, C, nt, lane, lo, pr);
+    if (lane < C) {
+      const long o = ((long)g * a.B + b) * C + lane;
+      if (a.logits) a.logits[o] = lo;
+      if (a.proba) a.proba[o] = pr;
+      ps[g][lane] = pr;
+    }
+    // the vote: scan the classes in ascending order, replace only on a strict >
+    float best = __shfl(pr, 0);
+    int am = 0;
+#pragma unroll
+    for (int c = 1; c < HEAD_MAXC; ++c) {
+      const float v = __shfl(pr, c);
+      if (c < C && v > best) { best = v; am = c; }
+    }
+    if (lane == 0) arg[g] = am;
+  }
+  __syncthreads();
+  if (wave == 0 && lane < C) {
+    int n = 0;
+    for (int g = 0; g < a.G; ++g) n += arg[g] == lane ? 1 : 0;
+    a.ens[(long)b * C + lane] = ensemble_mean(a.weight, ps, a.G, lane);
+    a.votes[(long)b * C + lane] = n;
   }
 }
 
@@ -1059,6 +1130,14 @@ int gt_head_predict(const HeadPredictArgs* a, hipStream_t stream) {
   return (int)hipGetLastError();
 }
 
+int gt_head_ensemble(const HeadEnsembleArgs* a, hipStream_t stream) {
+  if (a->C < 1 || a->C > HEAD_MAXC || a->G < 1 || a->G > ENS_MAXG || a->B < 1) return -1;
+  if (a->Up < 16 || a->Up % 16) return -2;
+  if (!a->plog || !a->b2 || !a->weight || !a->ens || !a->votes) return -3;
+  hipLaunchKernelGGL(head_ensemble_kernel, dim3(a->B), dim3(256), 0, stream, *a);
+  return (int)hipGetLastError();
+}
+
 int gt_dense_dgrad(const DenseDgradArgs* a, hipStream_t stream) {
   if (a->Fp % 64 && a->Fp % 8) return -1;
   if (a->unpool_mask && (a->Cp % 8 || a->Hs % 2 || a->Ws % 2 || (long)(a->Hs / 2) * (a->Ws / 2) * a->Cp != a->Fp))
@@ -1102,6 +1181,7 @@ int gt_adam_block_elems() { return ADAM_BLK; }
 size_t gt_sizeof_dense_fwd_args() { return sizeof(DenseFwdArgs); }
 size_t gt_sizeof_head_args() { return sizeof(HeadArgs); }
 size_t gt_sizeof_head_predict_args() { return sizeof(HeadPredictArgs); }
+size_t gt_sizeof_head_ensemble_args() { return sizeof(HeadEnsembleArgs); }
 size_t gt_sizeof_dense_dgrad_args() { return sizeof(DenseDgradArgs); }
 size_t gt_sizeof_dense_wgrad_args() { return sizeof(DenseWgradAdamArgs); }
 

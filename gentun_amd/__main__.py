@@ -7,7 +7,9 @@
 Multi-GPU: launch the same command under ``torchrun --nproc-per-node N``;
 rank 0 runs the GA, every rank is an evaluator (RCCL over xGMI). Runs are
 checkpointed per generation with ``--checkpoint-dir`` and resumed with
-``--resume``.
+``--resume``. ``cnn --save-model PATH`` refits the fittest genome on all rows and writes the classifier;
+``cnn --save-ensemble PATH --ensemble-size K`` does so for the K fittest distinct genomes of the last evaluated
+generation, as one ensemble.
 """
 
 import argparse
@@ -98,7 +100,9 @@ def _release_evaluators(population, timeout_s):
     return bool(done)
 
 
-def _run_search(args, species, x, y, extra, maximize):
+def _run_search(args, species, x, y, extra, maximize, keep=None):
+    """Run the search; rank 0 prints and returns the result line (other ranks: None). ``keep`` (a dict)
+    receives the last evaluated generation as ``keep["population"]``."""
     from . import GeneticAlgorithm, RussianRouletteGA
     from .metrics import EventLog
     from .parallel import LocalBatchEvaluator, from_env
@@ -165,6 +169,8 @@ def _run_search(args, species, x, y, extra, maximize):
         raise
     ga.population.shutdown()
     comm.finish()
+    if keep is not None:
+        keep["population"] = ga.evaluated_population
     out = {"best_fitness": best.get_fitness(), "best_genes": best.get_genes(),
            "history": [{k: h[k] for k in ("generation", "best_fitness", "evals", "wall_s", "candidates_per_hour")}
                        for h in ga.history]}
@@ -190,9 +196,13 @@ def cmd_cnn(args):
                  epochs=_ints(args.epochs), learning_rate=_floats(args.lr), batch_size=args.batch, loss=args.loss,
                  seed=args.seed, optimizer=args.optimizer, momentum=args.momentum, dtype=args.dtype,
                  reset=args.fold_reset, batching=args.batching, batch_norm=args.batch_norm)
-    out = _run_search(args, GeneticCnnIndividual, x, y, extra, maximize=True)
+    keep = {}
+    out = _run_search(args, GeneticCnnIndividual, x, y, extra, maximize=True, keep=keep)
     if out is not None and args.save_model:
         print(json.dumps(save_cnn_model(args.save_model, x, y, out["best_genes"], extra, device=_device())))
+    if out is not None and args.save_ensemble:
+        print(json.dumps(save_cnn_ensemble(args.save_ensemble, x, y, keep["population"], args.ensemble_size, extra,
+                                           device=_device())))
     return out
 
 
@@ -204,6 +214,20 @@ def save_cnn_model(path, x, y, genes, extra, device=None):
     clf = model.fit()
     clf.save(path)
     return {"saved_model": path, "genes": clf.genes, "metrics": clf.metrics}
+
+
+def save_cnn_ensemble(path, x, y, population, size, extra, device=None):
+    """``--save-ensemble`` of the ``cnn`` sub-command (rank 0): refit the ``size`` fittest distinct genomes of
+    the last evaluated generation on all rows with the search's own settings, as one ensemble, and write it
+    (.npz). Returns the line that is printed."""
+    from .models.cnn_ensemble import fit_ensemble, top_genomes
+    genomes = top_genomes(population, size)
+    if not genomes:
+        raise SystemExit("--save-ensemble: the final population holds no evaluated individual")
+    ens = fit_ensemble(x, y, genomes, device=device, **extra)
+    ens.save(path)
+    return {"saved_ensemble": path, "genes": [m.genes for m in ens.members], "metrics": ens.metrics,
+            "member_metrics": [m.metrics for m in ens.members]}
 
 
 def cmd_xgb(args):
@@ -290,6 +314,11 @@ def main(argv=None):
                    help="conv -> BatchNorm -> ReLU in every node (not in the reference network; off by default)")
     c.add_argument("--save-model", default=None, metavar="PATH",
                    help="after the search, refit the fittest individual on all rows and write the classifier (.npz)")
+    c.add_argument("--save-ensemble", default=None, metavar="PATH",
+                   help="after the search, refit the fittest distinct individuals of the final generation on all "
+                        "rows and write them as one ensemble (.npz)")
+    c.add_argument("--ensemble-size", type=int, default=3, metavar="K",
+                   help="members of --save-ensemble (1 to 64; fewer when fewer distinct genomes were evaluated)")
     c.set_defaults(fn=cmd_cnn)
     x = sub.add_parser("xgb", help="GBDT (XGBoost-style) hyper-parameter search")
     _common(x)

@@ -45,6 +45,7 @@ class GeneticAlgorithm(object):
         self.verbose = verbose
         self.history = []
         self.best_individual = None
+        self.evaluated_population = None     # the last generation whose fitnesses are all known
 
     # ------------------------------------------------------------ utilities
     def get_population_type(self):
@@ -70,6 +71,7 @@ class GeneticAlgorithm(object):
         self._say("Fittest individual is:", str(fittest),
                   "Fitness value is: {}\n".format(round(fittest.get_fitness(), 4)))
         fits = [ind.get_fitness() for ind in self.population]
+        self.evaluated_population = self.population
         rec = {
             "generation": self.generation,
             "best_fitness": fittest.get_fitness(),

@@ -163,6 +163,13 @@ class HeadPredictArgs(C.Structure):
     _fields_ = [("plog", P), ("b2", P), ("logits", P), ("proba", P), ("G", I), ("B", I), ("Up", I), ("C", I)]
 
 
+class HeadEnsembleArgs(C.Structure):
+    """csrc/hip/cnn_dense.hip HeadEnsembleArgs: the members' logits and probabilities (optional), their
+    weighted mean and their votes (gt_head_ensemble)."""
+    _fields_ = [("plog", P), ("b2", P), ("weight", P), ("logits", P), ("proba", P), ("ens", P), ("votes", P),
+                ("G", I), ("B", I), ("Up", I), ("C", I)]
+
+
 class DenseDgradArgs(C.Structure):
     _fields_ = [("dH", P), ("wt", P), ("dx", P), ("G", I), ("B", I), ("Fp", I), ("Up", I), ("prec", I),
                 ("wps", C.c_long), ("unpool_mask", P), ("unpool_x0", P), ("unpool_x1", P), ("unpool_sel", P),
@@ -273,6 +280,10 @@ def lib():
         L.gt_head_predict.restype = I
         L.gt_sizeof_head_predict_args.restype = C.c_size_t
         assert L.gt_sizeof_head_predict_args() == C.sizeof(HeadPredictArgs), "HeadPredictArgs ABI mismatch"
+        L.gt_head_ensemble.argtypes = [C.POINTER(HeadEnsembleArgs), P]
+        L.gt_head_ensemble.restype = I
+        L.gt_sizeof_head_ensemble_args.restype = C.c_size_t
+        assert L.gt_sizeof_head_ensemble_args() == C.sizeof(HeadEnsembleArgs), "HeadEnsembleArgs ABI mismatch"
         L.gt_adam_segments.argtypes = [C.POINTER(AdamArgs), I, P]
         L.gt_adam_segments.restype = I
         L.gt_step_begin.argtypes = [P, P]

@@ -16,6 +16,7 @@
 #   bash tools/gpu.sh gbdt-shap               Booster.predict(pred_contribs=True): GPU SHAP kernel vs the CPU predictor (ROWS= FEATURES= TREES= DEPTH= THREADS=)
 #   bash tools/gpu.sh gbdt-interactions       Booster.predict(pred_interactions=True): GPU kernel vs the CPU predictor (ROWS= FEATURES= TREES= DEPTH= THREADS= SPLITS=)
 #   bash tools/gpu.sh cnn-predict             CnnClassifier.predict: HIP predictor at 32 / 256 rows per launch vs stock torch on the GPU (ROWS= REPS=)
+#   bash tools/gpu.sh cnn-ensemble            CnnEnsemble.predict: one k-group launch set vs k predictors one by one vs stock torch; fit_ensemble vs k fits (ROWS= REPS= K= FIT_ROWS=)
 #   bash tools/gpu.sh rehearse                2-rank torchrun bench on one GPU (gloo control plane)
 #   bash tools/gpu.sh secondary               bench lines: reference fold semantics, torch comparator
 #
@@ -161,6 +162,11 @@ gbdt-interactions)
 cnn-predict)
   timeout -k 10 ${TIME:-420} python -u tools/bench_cnn_predict.py --rows ${ROWS:-10000} --reps ${REPS:-5} ${PREDICT_ARGS:-} \
     2>&1 | tail -3 | cut -c1-2400         # the result line; the script's status is the bench's (pipefail)
+  exit $? ;;
+cnn-ensemble)
+  timeout -k 10 ${TIME:-540} python -u tools/bench_cnn_ensemble.py --rows ${ROWS:-10000} --reps ${REPS:-5} --k ${K:-4,16} \
+    --fit-rows ${FIT_ROWS:-2000} ${ENSEMBLE_ARGS:-} \
+    2>&1 | tail -3 | cut -c1-4000         # the result line; the script's status is the bench's (pipefail)
   exit $? ;;
 rehearse)
   heartbeat
