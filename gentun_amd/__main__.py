@@ -178,6 +178,14 @@ def _run_search(args, species, x, y, extra, maximize, keep=None):
     return out
 
 
+def augment_setting(args):
+    """``TrainConfig.augment`` of ``--augment-shift N`` / ``--augment-flip`` (None when neither is given)."""
+    shift, flip = int(getattr(args, "augment_shift", 0) or 0), bool(getattr(args, "augment_flip", False))
+    if shift < 0:
+        raise SystemExit("--augment-shift must not be negative")
+    return {"shift": shift, "flip": flip} if (shift or flip) else None
+
+
 def cmd_cnn(args):
     from . import GeneticCnnIndividual
     from .utils.data import make_glyph_classification, make_variant_classification
@@ -195,7 +203,8 @@ def cmd_cnn(args):
                  dense_units=args.dense, dropout_probability=args.dropout, classes=args.classes, nfold=args.nfold,
                  epochs=_ints(args.epochs), learning_rate=_floats(args.lr), batch_size=args.batch, loss=args.loss,
                  seed=args.seed, optimizer=args.optimizer, momentum=args.momentum, dtype=args.dtype,
-                 reset=args.fold_reset, batching=args.batching, batch_norm=args.batch_norm)
+                 reset=args.fold_reset, batching=args.batching, batch_norm=args.batch_norm,
+                 augment=augment_setting(args))
     keep = {}
     out = _run_search(args, GeneticCnnIndividual, x, y, extra, maximize=True, keep=keep)
     if out is not None and args.save_model:
@@ -312,6 +321,10 @@ def main(argv=None):
     c.add_argument("--momentum", type=float, default=0.9, help="SGD momentum")
     c.add_argument("--batch-norm", action="store_true",
                    help="conv -> BatchNorm -> ReLU in every node (not in the reference network; off by default)")
+    c.add_argument("--augment-shift", type=int, default=0, metavar="N",
+                   help="training-time augmentation: random translation by up to N pixels with zero fill (0: off)")
+    c.add_argument("--augment-flip", action="store_true",
+                   help="training-time augmentation: random horizontal flip (off by default)")
     c.add_argument("--save-model", default=None, metavar="PATH",
                    help="after the search, refit the fittest individual on all rows and write the classifier (.npz)")
     c.add_argument("--save-ensemble", default=None, metavar="PATH",

@@ -276,7 +276,9 @@ class GeneticCnnIndividual(Individual):
     (False = the reference network; True = conv -> BatchNorm -> ReLU in every
     node, Keras BatchNormalization defaults) and ``verbose`` (print the
     reference's "KFold i/n" / "Training N epochs with learning rate lr" lines,
-    keras_models.py:134,137).
+    keras_models.py:134,137) and ``augment`` (None = the reference's training on the raw
+    images; ``{"shift": s, "flip": bool}`` = the Genetic-CNN paper's random translation
+    with zero fill and random horizontal flip, re-drawn every step on the device).
     """
 
     def __init__(self, x_train, y_train, genome=None, genes=None, crossover_rate=0.3, mutation_rate=0.1,
@@ -285,7 +287,7 @@ class GeneticCnnIndividual(Individual):
                  nfold=5, epochs=(3,), learning_rate=(1e-3,), batch_size=32,
                  loss='bce_compat', dtype='fp32', seed=0, backend=None, device=None, optimizer='adam',
                  momentum=0.9, reset='kernels', batching='keras', batch_norm=False, verbose=False,
-                 pad_images=True):
+                 pad_images=True, augment=None):
         if genome is None:
             genome = {'S_{}'.format(i + 1): k * (k - 1) // 2 for i, k in enumerate(nodes)}
         if genes is None:
@@ -320,6 +322,8 @@ class GeneticCnnIndividual(Individual):
         self.verbose = verbose
         # HIP executor: 28 x 28 stored zero-padded to 32 x 32 for the shape-specialised kernels
         self.pad_images = bool(pad_images)
+        # training-time augmentation: None or {"shift": s, "flip": bool} (TrainConfig.augment)
+        self.augment = None if augment is None else dict(augment)
 
     @staticmethod
     def generate_random_genes(genome):
@@ -338,7 +342,7 @@ class GeneticCnnIndividual(Individual):
                                seed=self.seed, backend=self.backend, device=device or self.device,
                                optimizer=self.optimizer, momentum=self.momentum, reset=self.reset,
                                batching=self.batching, batch_norm=self.batch_norm,
-                               verbose=self.verbose, pad_images=self.pad_images)
+                               verbose=self.verbose, pad_images=self.pad_images, augment=self.augment)
 
     def cost(self):
         """Relative training cost (forward FLOPs/sample); LPT scheduling key."""
@@ -377,6 +381,7 @@ class GeneticCnnIndividual(Individual):
             'batch_norm': self.batch_norm,
             'verbose': self.verbose,
             'pad_images': self.pad_images,
+            'augment': self.augment,
         }
 
     def mutate(self):

@@ -93,11 +93,55 @@ def graph_or_eager(nstreams, env=None):
     return False
 
 
+def normalize_augment(augment, hw=None):
+    """``None`` or ``{"shift": s, "flip": bool}`` with both keys present; ``ValueError`` on unknown keys,
+    a shift that is negative (or, given the real image size ``hw``, not below ``min(H, W)``) and on a
+    setting that transforms nothing."""
+    if augment is None:
+        return None
+    if not isinstance(augment, dict):
+        raise ValueError("augment must be None or a dict with the keys 'shift' and / or 'flip'")
+    unknown = sorted(set(augment) - {"shift", "flip"})
+    if unknown:
+        raise ValueError("augment: unknown keys {}".format(unknown))
+    shift, flip = augment.get("shift", 0), augment.get("flip", False)
+    if isinstance(shift, bool) or not isinstance(shift, (int, np.integer)) or shift < 0:
+        raise ValueError("augment: shift must be a non-negative integer")
+    if not isinstance(flip, (bool, np.bool_)):
+        raise ValueError("augment: flip must be a bool")
+    if shift == 0 and not flip:
+        raise ValueError("augment: {'shift': 0, 'flip': False} transforms nothing; pass None")
+    if hw is not None and shift >= min(hw):
+        raise ValueError("augment: shift {} must be below min(H, W) = {} of the image".format(shift, min(hw)))
+    return {"shift": int(shift), "flip": bool(flip)}
+
+
+def augment_images(x, dy, dx, flip, hw_real):
+    """The augmentation of a stack of images ``x [..., H, W]`` (any leading dimensions; H x W may be a
+    zero-padded extent around the real ``hw_real``) under per-image draws ``dy, dx, flip`` (integer tensors
+    of the leading shape): ``out[i, j] = x[i - dy, f(j - dx)]`` inside the real extent, exact zeros outside
+    it; ``f(u) = Wr - 1 - u`` where ``flip``. Pure indexing: the values are moved, never changed."""
+    Hr, Wr = hw_real
+    H, W = x.shape[-2:]
+    lead = x.shape[:-2]
+    ii = torch.arange(H, device=x.device).view((1,) * len(lead) + (H,))
+    jj = torch.arange(W, device=x.device).view((1,) * len(lead) + (W,))
+    si = ii - dy[..., None]
+    u = jj - dx[..., None]
+    rok = (ii < Hr) & (si >= 0) & (si < Hr)
+    cok = (jj < Wr) & (u >= 0) & (u < Wr)
+    sj = torch.where(flip[..., None] != 0, Wr - 1 - u, u)
+    si, sj = si.clamp(0, H - 1), sj.clamp(0, W - 1)
+    out = torch.take_along_dim(x, si[..., :, None].expand(lead + (H, W)), dim=-2)
+    out = torch.take_along_dim(out, sj[..., None, :].expand(lead + (H, W)), dim=-1)
+    return torch.where(rok[..., :, None] & cok[..., None, :], out, torch.zeros((), dtype=x.dtype, device=x.device))
+
+
 class TrainConfig(object):
     def __init__(self, epochs=(3,), learning_rate=(1e-3,), batch_size=32, dropout=0.5, loss="bce_compat",
                  dtype="fp32", seed=0, use_graph=None, eval_batch=1000, optimizer="adam", momentum=0.9,
                  reset="kernels", batching="keras", batch_norm=False, bn_momentum=0.99, bn_eps=1e-3,
-                 dp_group=None, verbose=False, nfold=None, pad_images=True):
+                 dp_group=None, verbose=False, nfold=None, pad_images=True, augment=None):
         if isinstance(epochs, int):
             epochs = (epochs,)
         if isinstance(learning_rate, (int, float)):
@@ -145,6 +189,9 @@ class TrainConfig(object):
         # HIP executor: store a slightly-smaller-than-power-of-two image zero-padded so every stage
         # runs the shape-specialised kernels (ops/cnn_kernels.padded_hw: MNIST 28 x 28 -> 32 x 32)
         self.pad_images = bool(pad_images)
+        # optional training-time augmentation (off by default): a random translation by up to ``shift``
+        # pixels with zero fill and a random horizontal flip, drawn per step and batch row on the device
+        self.augment = normalize_augment(augment)
 
     def total_epochs(self):
         return sum(self.epochs)
@@ -251,6 +298,10 @@ class FoldJob(object):
         self.member_seeds = [_rng.stable_hash("cnn", cfg.seed, sorted(p.genes.items())) & 0x7FFFFFFFFFFF
                              for p, _, _ in members]
         self.base_seed = self.member_seeds[0]
+        # augmentation (cfg.augment): per-group 32-bit keys shared with the dropout stream of the HIP executor;
+        # with the fold id, the global step and the full-batch row they fix every draw (utils/rng.aug_draws)
+        self.aug = normalize_augment(getattr(cfg, "augment", None), hw=self.plan.input_shape[:2])
+        self.aug_seeds = [_rng.stable_hash(self.member_seeds[c], "dropout") & 0xFFFFFFFF for c in self.gmember]
         # device index tables
         maxn = max(ntr)
         tm = np.zeros((self.G, maxn), np.int64)
@@ -663,6 +714,7 @@ class TorchFoldJob(FoldJob):
         self.capture_ok = False
         self.amp = (self.cfg.dtype == "bf16") and self.device.type == "cuda"
         self.drop_gen = None
+        self.global_step = 0          # train steps of this job so far (never reset: keys the augmentation draws)
         # BatchNorm running statistics per conv: [2 (mean, var)][G][C]
         self.bn_run = {st.name: torch.zeros((2, G, st.cout), device=self.device) for st in self._conv_specs()} \
             if self.cfg.batch_norm else {}
@@ -833,6 +885,19 @@ class TorchFoldJob(FoldJob):
         C, H, W = xb.shape[1:]
         return xb.view(G, Bn, C, H, W).permute(1, 0, 2, 3, 4).reshape(Bn, G * C, H, W)
 
+    def _augment(self, xb, row_off=0):
+        """The training batch ``xb [B, G*C, H, W]`` (rows ``row_off ..`` of the full batch) under the
+        augmentation of this step: draws keyed by (group key, fold id, global step, full-batch row)."""
+        G = self.G
+        Bn, GC, H, W = xb.shape
+        keys = np.asarray([_rng.aug_key(s, f) for s, f in zip(self.aug_seeds, self.fold_ids)], np.uint64)
+        rows = np.arange(row_off, row_off + Bn, dtype=np.uint64)
+        dy, dx, fl = _rng.aug_draws(keys[None, :], self.global_step, rows[:, None], self.aug["shift"],
+                                    self.aug["flip"])                           # [B, G]
+        dy, dx, fl = (torch.from_numpy(np.ascontiguousarray(v)).to(xb.device)[:, :, None] for v in (dy, dx, fl))
+        out = augment_images(xb.view(Bn, G, GC // G, H, W), dy, dx, fl, (H, W))
+        return out.reshape(Bn, GC, H, W)
+
     def _dp(self):
         """(group, rank, world, first row, end row) of the data-parallel slice."""
         grp = self.cfg.dp_group
@@ -855,7 +920,10 @@ class TorchFoldJob(FoldJob):
         wt = (rows < nval).float() / nval.clamp_min(1.0)
         if dp is not None:                           # this rank's rows of every group's batch
             idx, wt = idx[:, dp[3]:dp[4]], wt[:, dp[3]:dp[4]]
+        self.global_step += 1                        # the HIP executor's StepState.global_step after gt_step_begin
         xb = self._gather(idx)
+        if self.aug is not None:
+            xb = self._augment(xb, dp[3] if dp is not None else 0)
         yb = self.data.onehot.index_select(0, idx.reshape(-1)).view(self.G, idx.shape[1], -1)
         self.flat.grad.zero_()
         if self.amp:

@@ -16,8 +16,9 @@ population size and each launch is ``Q`` times larger -- the size at which
 
 Step (one HIP graph, replayed epochs x steps times):
 
-  step_begin -> per stage: conv IN (first stage gathers the batch from the
-  device-resident dataset), conv N_0..N_{K-1} (only groups whose node is
+  step_begin -> [cfg.augment: gt_augment writes the shifted / flipped batch] ->
+  per stage: conv IN (first stage gathers the batch from the device-resident
+  dataset, or reads the augmented batch), conv N_0..N_{K-1} (only groups whose node is
   active; fused N-ary Add of the node's predecessors), conv OUT (groups
   whose stage has a DAG), pool (per group: OUT or, without a DAG, IN) ->
   dense_fwd (+ReLU+dropout+partial logits) -> head (softmax + loss grad +
@@ -216,6 +217,9 @@ class HipPopJob(FoldJob):
             return
         if self.bn:
             raise ValueError("data parallelism with BatchNorm would need synchronised batch statistics")
+        if self.aug is not None:
+            raise ValueError("augment with dp_group is not supported by the HIP executor (the torch executor "
+                             "supports it); train without data parallelism or without augmentation")
         import torch.distributed as dist
         world, rank = dist.get_world_size(grp), dist.get_rank(grp)
         B = self.B
@@ -568,6 +572,39 @@ class HipPopJob(FoldJob):
         t = (self.grad if grad else self.act).get(name)
         return t.data_ptr() if t is not None else 0       # a node no group has: never selected
 
+    def _build_augment(self):
+        """``cfg.augment``: the augmented batch, the gt_augment launch (csrc/hip/cnn_augment.hip) that
+        fills it from the dataset every step, and the training copy of the forward launches whose first
+        conv reads it. The conv and wgrad kernels keep their gather path (so the same shape-specialised
+        kernels run): ``in[0]`` is the augmented batch and the table is the constant ``g * B + b``.
+        ``self.fwd_ops`` stays the dataset-reading list the evaluation launches are copied from. Off
+        (None): nothing is allocated and the training launches ARE ``self.fwd_ops``."""
+        self.aug_args = self.aug_x = self.aug_table = None
+        self.train_fwd_ops = self.fwd_ops
+        if self.aug is None:
+            return
+        Q, B, dev = self.Q, self.B, self.device
+        h0r, w0r, c0 = self.plan.input_shape
+        hp, wp = self.pad_hw or (h0r, w0r)
+        self.aug_x = torch.zeros((Q * B, hp, wp, pad8(c0)), dtype=self.adt, device=dev)
+        self.aug_table = torch.arange(Q * B, dtype=torch.int64, device=dev).view(1, Q, B).repeat(
+            self.steps_per_epoch, 1, 1).contiguous()
+        a = K.AugArgs()
+        a.src, a.out = self.data.x.data_ptr(), self.aug_x.data_ptr()
+        a.gather, a.st = self.epoch_idx.data_ptr(), self.state.data_ptr()
+        a.fold_ids, a.seeds = self.fold_ids_t.data_ptr(), self.drop_seeds_t.data_ptr()
+        a.row_off = 0                     # data parallelism with augmentation is refused (_setup_dp)
+        a.Q, a.B, a.Hp, a.Wp, a.Hr, a.Wr, a.Cp = Q, B, hp, wp, h0r, w0r, pad8(c0)
+        a.shift, a.flip, a.prec = self.aug["shift"], 1 if self.aug["flip"] else 0, self.prec
+        self.aug_args = a
+        ops = []
+        for kind, c, Lr in self.fwd_ops:
+            if kind == "conv" and c.gather:
+                c = K.ConvArgs.from_buffer_copy(c)
+                c.inp[0], c.gather = self.aug_x.data_ptr(), self.aug_table.data_ptr()
+            ops.append((kind, c, Lr))
+        self.train_fwd_ops = ops
+
     def _build_args(self):
         """Pre-build every launch's argument struct (pointers are fixed)."""
         Q, B = self.Q, self.B
@@ -603,6 +640,7 @@ class HipPopJob(FoldJob):
                                      self.act[st.pool].data_ptr(), Q * B, B, hh, ww, cc), st.pmask.data_ptr()))
             self.pool_fused.append(fused)
             self.fwd_ops.extend(ops)
+        self._build_augment()
         prec = self.prec
         # ---- head
         df = K.DenseFwdArgs()
@@ -704,6 +742,8 @@ class HipPopJob(FoldJob):
                 for i, n in enumerate(wslots):
                     wa.inp[i] = self._slot_ptr(n)
                 wa.gather = gather_train if first else 0
+                if first and self.aug_args is not None:      # the augmented batch through its constant table
+                    wa.inp[0], wa.gather = self.aug_x.data_ptr(), self.aug_table.data_ptr()
                 wa.st = self.state.data_ptr()
                 wa.dz = self.grad[L.name].data_ptr()
                 wa.part_w, wa.part_b = L.part_w.data_ptr(), L.part_b.data_ptr()
@@ -924,7 +964,9 @@ class HipPopJob(FoldJob):
         :class:`~gentun_amd.ops.cnn_kernels.StepProgram`."""
         main = None
         plan = [("k", "gt_step_begin", (self.state.data_ptr(),), main, "step_begin")]
-        plan += self._fwd_plan(self.fwd_ops)
+        if self.aug_args is not None:
+            plan.append(("k", "gt_augment", (self.aug_args,), main, "augment"))
+        plan += self._fwd_plan(self.train_fwd_ops)
         plan += [("k", "gt_dense_fwd", (self.dense_fwd_args,), main, "dense_fwd"),
                  ("k", "gt_head", (self.head_args,), main, "head"),
                  ("k", "gt_dense_dgrad", (self.dense_dgrad_args,), main, "dense_dgrad")]   # reads W1 before its update

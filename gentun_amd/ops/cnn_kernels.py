@@ -247,7 +247,14 @@ PROG_OPS = {"record": 0, "wait": 1, "gt_step_begin": 2, "gt_conv_fwd": 3, "gt_co
             "gt_wgrad_reduce": 5, "gt_bn_fwd": 6, "gt_bn_bwd": 7, "gt_dense_fwd": 8, "gt_head": 9,
             "gt_dense_dgrad": 10, "gt_dense_wgrad_adam": 11, "gt_adam_segments": 12, "gt_pool_fwd": 13,
             "gt_pool_fwd_mask": 14, "gt_pool_bwd_mask": 15, "gt_wino_wtrans": 16,
-            "gt_conv_wfrag": 17}
+            "gt_conv_wfrag": 17, "gt_augment": 18}
+
+
+class AugArgs(C.Structure):
+    """csrc/hip/cnn_augment.hip AugArgs: shift-and-flip augmentation of the gathered training batch."""
+    _fields_ = [("src", P), ("out", P), ("gather", P), ("st", P), ("fold_ids", P), ("seeds", P),
+                ("seed", C.c_uint), ("row_off", I), ("Q", I), ("B", I), ("Hp", I), ("Wp", I), ("Hr", I), ("Wr", I),
+                ("Cp", I), ("shift", I), ("flip", I), ("prec", I)]
 
 
 class InitSeg(C.Structure):
@@ -276,6 +283,10 @@ def lib():
             fn = getattr(L, name)
             fn.argtypes = [C.POINTER(BnArgs), P]
             fn.restype = I
+        L.gt_augment.argtypes = [C.POINTER(AugArgs), P]
+        L.gt_augment.restype = I
+        L.gt_sizeof_aug_args.restype = C.c_size_t
+        assert L.gt_sizeof_aug_args() == C.sizeof(AugArgs), "AugArgs ABI mismatch"
         L.gt_head_predict.argtypes = [C.POINTER(HeadPredictArgs), P]
         L.gt_head_predict.restype = I
         L.gt_sizeof_head_predict_args.restype = C.c_size_t

@@ -17,6 +17,7 @@
 #   bash tools/gpu.sh gbdt-interactions       Booster.predict(pred_interactions=True): GPU kernel vs the CPU predictor (ROWS= FEATURES= TREES= DEPTH= THREADS= SPLITS=)
 #   bash tools/gpu.sh cnn-predict             CnnClassifier.predict: HIP predictor at 32 / 256 rows per launch vs stock torch on the GPU (ROWS= REPS=)
 #   bash tools/gpu.sh cnn-ensemble            CnnEnsemble.predict: one k-group launch set vs k predictors one by one vs stock torch; fit_ensemble vs k fits (ROWS= REPS= K= FIT_ROWS=)
+#   bash tools/gpu.sh cnn-augment             TrainConfig.augment: step time off / on (and the parent tree in ab_old/), gt_augment's kernel time (GROUPS_LIST= REPS= PROF_GROUPS= OUT=)
 #   bash tools/gpu.sh rehearse                2-rank torchrun bench on one GPU (gloo control plane)
 #   bash tools/gpu.sh secondary               bench lines: reference fold semantics, torch comparator
 #
@@ -168,6 +169,20 @@ cnn-ensemble)
     --fit-rows ${FIT_ROWS:-2000} ${ENSEMBLE_ARGS:-} \
     2>&1 | tail -3 | cut -c1-4000         # the result line; the script's status is the bench's (pipefail)
   exit $? ;;
+cnn-augment)
+  # step time without / with augmentation (and in ab_old/, the built parent tree, when it is there), then the
+  # kernel's own time from a kernel trace of one child run of its own; files are kept under $OUT
+  out=${OUT:-/tmp/cnn_augment}; heartbeat; mkdir -p $out; rocprof_env; rm -rf /tmp/prof_aug
+  parent=""; [ -d ab_old/gentun_amd/_native ] && parent="--parent ab_old"
+  timeout -k 10 ${TIME:-700} python -u tools/bench_augment.py --groups ${GROUPS_LIST:-25,80} --reps ${REPS:-3} $parent \
+    > $out/bench.json 2> $out/bench.err &&
+  cut -c1-3000 $out/bench.json &&
+  timeout -k 10 300 rocprofv3 --kernel-trace --stats -d /tmp/prof_aug -o run --output-format csv -- \
+    python3 tools/bench_augment.py --child .:${PROF_GROUPS:-25}:1 > $out/prof.log 2>&1 &&
+  find /tmp/prof_aug -name "*kernel_stats.csv" -exec cp {} $out/kernel_stats.csv \; &&
+  grep -E "Name|augment" $out/kernel_stats.csv | cut -c1-300; rc=$?
+  [ $rc -eq 0 ] || tail -5 $out/bench.err $out/prof.log 2>/dev/null
+  exit $rc ;;
 rehearse)
   heartbeat
   GENTUN_DIST_BACKEND=gloo timeout -k 10 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node ${N:-2} \
@@ -189,5 +204,5 @@ secondary)
     cat gpurun_out/sec/torch.json
   fi ;;
 *)
-  sed -n 2,21p "$0"; exit 2 ;;
+  sed -n 2,22p "$0"; exit 2 ;;
 esac
