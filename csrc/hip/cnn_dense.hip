@@ -561,6 +561,74 @@ __global__ void __launch_bounds__(256) head_ensemble_kernel(HeadEnsembleArgs a) 
   }
 }
 
+// Test-time augmentation head (models/cnn_fitted.py, models/cnn_ensemble.py): the launch's B rows are V views
+// of R raw rows, view v of raw row r at launch row v * R + r (gt_tta_views, cnn_tta.hip). Per member the
+// logits and probabilities of a raw row are the means over its views; the members then combine as in
+// gt_head_ensemble. A single classifier is the ensemble of one member with weight 1.0f (1.0f * p is p).
+struct HeadTtaArgs {
+  const float* plog;       // [G][Up/16][B][C] partial logits from dense_fwd (evaluation mode)
+  const float* b2;         // [G][C]
+  const float* weight;     // [G] fp32, normalised on the host
+  float* logits;           // [G][R][C] view means, may be null
+  float* proba;            // [G][R][C] view means, may be null
+  float* ens;              // [R][C]  weighted mean of the members' view-mean probabilities
+  int* votes;              // [R][C]  number of members whose view-mean probability peaks first at c
+  int G, B, Up, C;         // B: the launch's rows (plog's stride)
+  int R, V;                // raw rows, views: V * R <= B
+  float inv_v;             // fp32 1 / V, computed on the host
+};
+
+// One workgroup of 4 waves per raw row r; wave w serves members w, w + 4, ... For each it runs
+// head_predict_kernel's wave on launch rows r, R + r, ... (the same helper: every per-view logit and
+// probability is the float gt_head_predict writes for that row), sums them in view order (acc = p_0, then
+// acc = acc + p_v) and multiplies by inv_v -- the add and the multiply rounded separately, the host's numpy
+// fp32 combine -- and leaves the mean probability and its vote in LDS. With V = 1, acc * 1.0f is acc: the
+// kernel then writes what head_ensemble_kernel writes. After the barrier wave 0 combines the members.
+__global__ void __launch_bounds__(256) head_tta_kernel(HeadTtaArgs a) {
+  __shared__ float ps[ENS_MAXG][HEAD_MAXC];
+  __shared__ int arg[ENS_MAXG];
+  const int r = blockIdx.x, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int C = a.C, nt = a.Up / 16;
+  for (int g = wave; g < a.G; g += 4) {
+    const float* pl = a.plog + ((long)g * nt * a.B + r) * C;
+    float slo = 0.f, spr = 0.f;
+    for (int v = 0; v < a.V; ++v) {
+      float lo, pr;
+      head_row_softmax(pl + (long)v * a.R * C, a.b2 + (long)g * C, a.B, C, nt, lane, lo, pr);
+      slo = v ? slo + lo : lo;         // acc = p_0, not 0 + p_0: the sign of a zero is p_0's
+      spr = v ? spr + pr : pr;
+    }
+    float mlo, mpr;
+    {
+#pragma clang fp contract(off)
+      mlo = slo * a.inv_v;
+      mpr = spr * a.inv_v;
+    }
+    if (lane < C) {
+      const long o = ((long)g * a.R + r) * C + lane;
+      if (a.logits) a.logits[o] = mlo;
+      if (a.proba) a.proba[o] = mpr;
+      ps[g][lane] = mpr;
+    }
+    // the vote of the mean: classes in ascending order, replaced only on a strict >
+    float best = __shfl(mpr, 0);
+    int am = 0;
+#pragma unroll
+    for (int c = 1; c < HEAD_MAXC; ++c) {
+      const float v = __shfl(mpr, c);
+      if (c < C && v > best) { best = v; am = c; }
+    }
+    if (lane == 0) arg[g] = am;
+  }
+  __syncthreads();
+  if (wave == 0 && lane < C) {
+    int n = 0;
+    for (int g = 0; g < a.G; ++g) n += arg[g] == lane ? 1 : 0;
+    a.ens[(long)r * C + lane] = ensemble_mean(a.weight, ps, a.G, lane);
+    a.votes[(long)r * C + lane] = n;
+  }
+}
+
 // (2) grid (ceil(Up/64), G): per 64-unit slice, dH = (dz W2^T) * scale * (h > 0),
 //     gb1 = sum_b dH, gW2 = h^T dz; block 0 also gb2 = sum_b dz.
 __global__ void __launch_bounds__(256) head_bwd_kernel(HeadArgs a) {
@@ -1138,6 +1206,16 @@ int gt_head_ensemble(const HeadEnsembleArgs* a, hipStream_t stream) {
   return (int)hipGetLastError();
 }
 
+int gt_head_tta(const HeadTtaArgs* a, hipStream_t stream) {
+  if (!a) return -3;
+  if (a->C < 1 || a->C > HEAD_MAXC || a->G < 1 || a->G > ENS_MAXG || a->B < 1) return -1;
+  if (a->Up < 16 || a->Up % 16) return -2;
+  if (!a->plog || !a->b2 || !a->weight || !a->ens || !a->votes) return -3;
+  if (a->R < 1 || a->V < 1 || a->V > 16 || (long)a->V * a->R > a->B) return -4;
+  hipLaunchKernelGGL(head_tta_kernel, dim3(a->R), dim3(256), 0, stream, *a);
+  return (int)hipGetLastError();
+}
+
 int gt_dense_dgrad(const DenseDgradArgs* a, hipStream_t stream) {
   if (a->Fp % 64 && a->Fp % 8) return -1;
   if (a->unpool_mask && (a->Cp % 8 || a->Hs % 2 || a->Ws % 2 || (long)(a->Hs / 2) * (a->Ws / 2) * a->Cp != a->Fp))
@@ -1182,6 +1260,7 @@ size_t gt_sizeof_dense_fwd_args() { return sizeof(DenseFwdArgs); }
 size_t gt_sizeof_head_args() { return sizeof(HeadArgs); }
 size_t gt_sizeof_head_predict_args() { return sizeof(HeadPredictArgs); }
 size_t gt_sizeof_head_ensemble_args() { return sizeof(HeadEnsembleArgs); }
+size_t gt_sizeof_head_tta_args() { return sizeof(HeadTtaArgs); }
 size_t gt_sizeof_dense_dgrad_args() { return sizeof(DenseDgradArgs); }
 size_t gt_sizeof_dense_wgrad_args() { return sizeof(DenseWgradAdamArgs); }
 

@@ -24,7 +24,7 @@ import math
 import numpy as np
 import torch
 
-from .cnn_fitted import CnnClassifier, predict_batch
+from .cnn_fitted import CnnClassifier, TtaState, predict_batch, tta_views
 
 FORMAT = "gentun-cnn-ensemble/1"
 OUTPUTS = ("proba", "label", "votes", "vote_label", "member_proba", "member_logits")
@@ -142,7 +142,7 @@ class CnnEnsemble(object):
         return ens
 
     # ------------------------------------------------------------ prediction
-    def predict(self, x, device=None, output="proba", batch=256, backend=None):
+    def predict(self, x, device=None, output="proba", batch=256, backend=None, tta=None):
         """One of ``OUTPUTS`` for ``x`` ``[n, H, W, C]`` (or one image), ``batch`` rows at a time:
 
         ``"proba"`` fp32 ``[n, classes]``, the weighted mean of the members' probabilities; ``"label"`` int64,
@@ -152,10 +152,14 @@ class CnnEnsemble(object):
 
         ``device`` None or ``"cpu"``, or ``backend="torch"``: every member's stock-torch forward and the
         combination in numpy fp32. A ``cuda`` device: :class:`HipEnsemblePredictor`. A short chunk is
-        filled with zero images and only the real rows are returned, as in ``CnnClassifier.predict``."""
-        return self.predict_outputs(x, (output,), device=device, batch=batch, backend=backend)[output]
+        filled with zero images and only the real rows are returned, as in ``CnnClassifier.predict``.
 
-    def predict_outputs(self, x, outputs=OUTPUTS, device=None, batch=256, backend=None):
+        ``tta`` (test-time augmentation, ``cnn_fitted.tta_views``): every member's probabilities and logits
+        become their means over the views, as in ``CnnClassifier.predict(tta=...)``; the weighted mean, the
+        votes and the labels are formed from those."""
+        return self.predict_outputs(x, (output,), device=device, batch=batch, backend=backend, tta=tta)[output]
+
+    def predict_outputs(self, x, outputs=OUTPUTS, device=None, batch=256, backend=None, tta=None):
         """``{name: array}`` of several ``OUTPUTS`` from one pass over ``x``."""
         outputs = tuple(outputs)
         for output in outputs:
@@ -164,15 +168,16 @@ class CnnEnsemble(object):
         if int(batch) < 1:
             raise ValueError("batch must be positive")
         x = self.members[0]._check_x(x)
+        views = tta_views(tta, self.input_shape)
         dev = torch.device("cpu" if device is None else device)
         if backend is None:
             backend = "hip" if dev.type == "cuda" else "torch"
         res = {}
         if backend == "hip":
             res = self.hip_predictor(dev, batch).run(x, members="member_proba" in outputs or
-                                                     "member_logits" in outputs)
+                                                     "member_logits" in outputs, views=views)
         elif backend == "torch":
-            kw = dict(device=dev, batch=int(batch), backend="torch")
+            kw = dict(device=dev, batch=int(batch), backend="torch", tta=views)
             res["member_proba"] = np.stack([np.asarray(m.predict(x, output="proba", **kw), np.float32)
                                             for m in self.members])
             if "member_logits" in outputs:
@@ -259,6 +264,7 @@ class HipEnsemblePredictor(object):
                 a.ens, a.votes = self.ens.data_ptr(), self.votes.data_ptr()
                 a.G, a.B, a.Up, a.C = k, EB, job.Up, C
                 self.heads[members] = a
+        self._tta = {}               # views -> TtaState, created on first use
 
     def _host(self, ens, EB):
         from . import cnn_engine as E
@@ -294,9 +300,19 @@ class HipEnsemblePredictor(object):
             self.stage[m:].zero_()
         self.stage[:m, :h, :w, :c].copy_(torch.from_numpy(chunk).to(self.device))
 
-    def run(self, x, members=False):
+    def tta_state(self, views):
+        """The cached ``TtaState`` of a view tuple over the ``k`` members and their weights."""
+        st = self._tta.get(views)
+        if st is None:
+            with torch.cuda.device(self.device):
+                st = self._tta[views] = TtaState(self, views, self.k, self.weight)
+        return st
+
+    def run(self, x, members=False, views=None):
         """``x`` [n, H, W, C] host fp32 -> ``{"proba", "votes"}`` (+ ``"member_proba"``, ``"member_logits"``)
-        as host arrays; the chunks' results gather on the device and are read back once."""
+        as host arrays; the chunks' results gather on the device and are read back once. With ``views`` (a
+        tuple of ``(dy, dx, flip)``) every member's outputs are the means over those views,
+        ``EB // len(views)`` rows per launch."""
         n, EB, k, C = x.shape[0], self.EB, self.k, self.classes
         ens = torch.empty((n, C), dtype=torch.float32, device=self.device)
         votes = torch.empty((n, C), dtype=torch.int32, device=self.device)
@@ -304,15 +320,23 @@ class HipEnsemblePredictor(object):
             logits = torch.empty((k, n, C), dtype=torch.float32, device=self.device)
             proba = torch.empty_like(logits)
         with torch.cuda.device(self.device):
-            for s in range(0, n, EB):
-                m = min(EB, n - s)
-                self.upload(x[s:s + m])
-                self.forward(members)
-                ens[s:s + m].copy_(self.ens[:m])
-                votes[s:s + m].copy_(self.votes[:m])
+            st = None if views is None else self.tta_state(tuple(views))
+            rows, res = (EB, self) if st is None else (st.R, st)     # rows per chunk, who holds its results
+            if st is not None and st.V * st.R < EB:
+                self.stage[st.V * st.R:].zero_()                     # rows no view is written to
+            for s in range(0, n, rows):
+                m = min(rows, n - s)
+                if st is None:
+                    self.upload(x[s:s + m])
+                    self.forward(members)
+                else:
+                    st.upload(x[s:s + m], self.hwc)
+                    st.forward(self, members, "ensemble")
+                ens[s:s + m].copy_(res.ens[:m])
+                votes[s:s + m].copy_(res.votes[:m])
                 if members:
-                    logits[:, s:s + m].copy_(self.logits[:, :m])
-                    proba[:, s:s + m].copy_(self.proba[:, :m])
+                    logits[:, s:s + m].copy_(res.logits[:, :m])
+                    proba[:, s:s + m].copy_(res.proba[:, :m])
             out = {"proba": ens.cpu().numpy(), "votes": votes.cpu().numpy()}
             if members:
                 out["member_logits"], out["member_proba"] = logits.cpu().numpy(), proba.cpu().numpy()

@@ -29,6 +29,86 @@ OUTPUTS = ("proba", "logits", "label")
 _BN_KINDS = ("gamma", "beta", "running_mean", "running_var")
 
 
+TTA_MAX_VIEWS = 16           # TTA_MAXV of csrc/hip/cnn_tta.hip
+
+
+def _is_int(v):
+    return isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
+
+
+def tta_views(tta, input_shape):
+    """The views ``((dy, dx, flip), ...)`` of a test-time augmentation setting for images of ``input_shape``
+    ``(H, W, C)``, as a tuple of int triples (``None`` for ``None``).
+
+    ``tta`` is an explicit sequence of 1 to 16 pairwise distinct views ``(dy, dx, flip)`` (integers with
+    ``|dy| < H`` and ``|dx| < W``; ``flip`` a bool or 0 / 1), returned as given, or the shorthand
+    ``{"shift": s, "flip": bool}`` of ``TrainConfig.augment`` (``0 <= s < min(H, W)``; either key may be
+    absent), which expands, identity first, to: for ``flip`` in (0, 1) if enabled else (0,), for
+    ``(dy, dx)`` in ``[(0, 0), (-s, 0), (s, 0), (0, -s), (0, s)]`` if ``s > 0`` else ``[(0, 0)]`` -- 1, 2, 5
+    or 10 views. ``ValueError`` on anything else."""
+    if tta is None:
+        return None
+    H, W = int(input_shape[0]), int(input_shape[1])
+    if isinstance(tta, dict):
+        unknown = sorted(set(tta) - {"shift", "flip"}, key=repr)
+        if unknown:
+            raise ValueError("tta: unknown keys {}".format(unknown))
+        shift, flip = tta.get("shift", 0), tta.get("flip", False)
+        if not _is_int(shift) or shift < 0:
+            raise ValueError("tta: shift must be a non-negative integer")
+        if not isinstance(flip, (bool, np.bool_)):
+            raise ValueError("tta: flip must be a bool")
+        if shift >= min(H, W):
+            raise ValueError("tta: shift {} must be below min(H, W) = {} of the image".format(shift, min(H, W)))
+        s = int(shift)
+        shifts = [(0, 0), (-s, 0), (s, 0), (0, -s), (0, s)] if s > 0 else [(0, 0)]
+        return tuple((dy, dx, f) for f in ((0, 1) if flip else (0,)) for dy, dx in shifts)
+    if isinstance(tta, (str, bytes)) or not isinstance(tta, (list, tuple, np.ndarray)):
+        raise ValueError("tta must be None, a sequence of (dy, dx, flip) views or a dict with the keys 'shift' "
+                         "and / or 'flip'")
+    if not 1 <= len(tta) <= TTA_MAX_VIEWS:
+        raise ValueError("tta: 1 to {} views, got {}".format(TTA_MAX_VIEWS, len(tta)))
+    views = []
+    for view in tta:
+        if isinstance(view, (str, bytes)) or not isinstance(view, (list, tuple, np.ndarray)) or len(view) != 3:
+            raise ValueError("tta: a view is (dy, dx, flip), got {!r}".format(view))
+        dy, dx, flip = view
+        if not _is_int(dy) or not _is_int(dx):
+            raise ValueError("tta: dy and dx must be integers, got {!r}".format(view))
+        if abs(int(dy)) >= H or abs(int(dx)) >= W:
+            raise ValueError("tta: view {!r} needs |dy| < {} and |dx| < {}".format(view, H, W))
+        if not (isinstance(flip, (bool, np.bool_)) or (_is_int(flip) and int(flip) in (0, 1))):
+            raise ValueError("tta: flip must be a bool or 0 / 1, got {!r}".format(view))
+        views.append((int(dy), int(dx), int(flip)))
+    if len(set(views)) != len(views):
+        raise ValueError("tta: the views must be pairwise distinct")
+    return tuple(views)
+
+
+def tta_transform(x, dy, dx, flip):
+    """View ``(dy, dx, flip)`` of images ``x [n, H, W, C]``: ``out[i, j] = x[i - dy, f(j - dx)]`` inside the
+    image, zeros outside it; ``f(u) = W - 1 - u`` where ``flip`` (flip first, then translate) -- training's
+    augmentation (csrc/hip/cnn_augment.hip) under a fixed draw. Slicing only: the values are moved, never
+    changed."""
+    n, H, W, _ = x.shape
+    src = x[:, :, ::-1] if flip else x
+    out = np.zeros_like(x)
+    out[:, max(dy, 0):H + min(dy, 0), max(dx, 0):W + min(dx, 0)] = \
+        src[:, max(-dy, 0):H - max(dy, 0), max(-dx, 0):W - max(dx, 0)]
+    return out
+
+
+def tta_combine(per_view):
+    """The mean over views of ``per_view`` (a sequence of equal-shape arrays) in view order and in their
+    dtype: ``acc = p[0]``, ``acc = acc + p[v]``, then ``acc * (1 / V)`` with ``1 / V`` rounded to that dtype
+    first -- the add and the multiply rounded separately, as ``gt_head_tta`` does on the device."""
+    acc = np.asarray(per_view[0])
+    one = acc.dtype.type
+    for p in per_view[1:]:
+        acc = acc + p
+    return (acc * (one(1) / one(len(per_view)))).astype(acc.dtype, copy=False)
+
+
 def predict_batch(batch):
     """Rows per launch of the HIP predictor: ``batch`` rounded up to a multiple of 32, at least 32 and
     at most 256 (the cap of ``HipPopJob.eval_batch``)."""
@@ -138,7 +218,7 @@ class CnnClassifier(object):
                 *(self.input_shape + (tuple(np.shape(x)),))))
         return np.ascontiguousarray(x, dtype=np.float32)
 
-    def predict(self, x, device=None, output="proba", batch=256, backend=None, dtype=None):
+    def predict(self, x, device=None, output="proba", batch=256, backend=None, dtype=None, tta=None):
         """Class probabilities (``"proba"``: softmax, fp32 ``[n, classes]``), ``"logits"`` or ``"label"``
         (int64: the most probable class, the lowest index on ties) of ``x`` ``[n, H, W, C]`` (or one
         ``[H, W, C]`` image), ``batch`` rows at a time.
@@ -147,21 +227,30 @@ class CnnClassifier(object):
         tests' oracle). A ``cuda`` device: the HIP predictor; ``backend="torch"`` the stock-torch forward
         there instead. Both paths fill a short chunk with zero images (to ``EB`` rows on the HIP path,
         to a multiple of 32 on the torch path) and return the real rows only, so a row's result does
-        not depend on how many rows are predicted with it."""
+        not depend on how many rows are predicted with it.
+
+        ``tta`` (test-time augmentation; see :func:`tta_views`): the logits / probabilities become the mean
+        over the views of the image, in view order in fp32 (:func:`tta_combine`), the label the first
+        maximum of the mean probabilities. The torch backend predicts each view in turn; the HIP predictor
+        builds the views on the device (``gt_tta_views``) and averages them in the head (``gt_head_tta``)."""
         if output not in OUTPUTS:
             raise ValueError("output {!r}: expected one of {}".format(output, OUTPUTS))
         if int(batch) < 1:
             raise ValueError("batch must be positive")
         x = self._check_x(x)
+        views = tta_views(tta, self.input_shape)
         dev = torch.device("cpu" if device is None else device)
         if backend is None:
             backend = "hip" if dev.type == "cuda" else "torch"
         if backend == "hip":
             if dtype is not None:
                 raise ValueError("dtype is an option of the torch backend")
-            logits, proba = self.hip_predictor(dev, batch).run(x)
-        elif backend == "torch":
+            logits, proba = self.hip_predictor(dev, batch).run(x, views=views)
+        elif backend == "torch" and views is None:
             logits, proba = self._torch_predict(x, dev, int(batch), dtype or torch.float32)
+        elif backend == "torch":
+            per = [self._torch_predict(tta_transform(x, *v), dev, int(batch), dtype or torch.float32) for v in views]
+            logits, proba = tta_combine([p[0] for p in per]), tta_combine([p[1] for p in per])
         else:
             raise ValueError("unknown backend {!r}".format(backend))
         if output == "logits":
@@ -333,6 +422,66 @@ def _import_hip(clf, job, g):
 # HIP predictor
 # ---------------------------------------------------------------------------
 
+class TtaState(object):
+    """What a HIP predictor (``HipPredictor`` or ``HipEnsemblePredictor``) adds for one tuple of test-time
+    augmentation views: the raw chunk buffer of ``R = EB // V`` images in the staging tensor's layout and
+    element type (zero outside the real extent), the arguments of ``gt_tta_views`` (raw chunk -> rows
+    ``v * R + r`` of the staging tensor) and of ``gt_head_tta`` (per member the mean over the views, then
+    the members' weighted mean and votes), and the outputs of ``R`` rows. The predictor's job, evaluation
+    launches and gather table are used as they are, at ``EB`` rows."""
+
+    def __init__(self, pred, views, G, weight):
+        K, job, stage, C = pred.K, pred.job, pred.stage, pred.classes
+        self.views, self.V = tuple(views), len(views)
+        self.R = R = pred.EB // self.V
+        if not 1 <= self.V <= K.TTA_MAXV or R < 1:
+            raise ValueError("{} views do not fit {} rows per launch".format(self.V, pred.EB))
+        dev = pred.device
+        self.raw = torch.zeros((R,) + tuple(stage.shape[1:]), dtype=stage.dtype, device=dev)
+        self.weight = weight
+        self.logits = torch.empty((G, R, C), dtype=torch.float32, device=dev)
+        self.proba = torch.empty_like(self.logits)
+        self.ens = torch.empty((R, C), dtype=torch.float32, device=dev)
+        self.votes = torch.empty((R, C), dtype=torch.int32, device=dev)
+        va = K.TtaViewArgs()
+        va.raw, va.out = self.raw.data_ptr(), stage.data_ptr()
+        va.R, va.V, va.rows = R, self.V, pred.EB
+        va.Hp, va.Wp, va.Cp = (int(d) for d in stage.shape[1:])
+        va.Hr, va.Wr = pred.hwc[0], pred.hwc[1]
+        va.prec = 1 if stage.dtype == torch.float32 else 0
+        for i, (dy, dx, flip) in enumerate(self.views):
+            va.dy[i], va.dx[i], va.flip[i] = dy, dx, flip
+        self.view_args = va
+        self.heads = {}
+        for members in (False, True):            # the member outputs are written on request only
+            a = K.HeadTtaArgs()
+            a.plog, a.b2, a.weight = pred.df.plog, job.views["b2"][0].data_ptr(), weight.data_ptr()
+            a.logits = self.logits.data_ptr() if members else 0
+            a.proba = self.proba.data_ptr() if members else 0
+            a.ens, a.votes = self.ens.data_ptr(), self.votes.data_ptr()
+            a.G, a.B, a.Up, a.C = G, pred.EB, job.Up, C
+            a.R, a.V, a.inv_v = R, self.V, float(np.float32(1) / np.float32(self.V))
+            self.heads[members] = a
+
+    def upload(self, chunk, hwc):
+        """``chunk`` [m <= R, H, W, C] host fp32 into the raw buffer; rows past ``m`` become zero images."""
+        m = chunk.shape[0]
+        h, w, c = hwc
+        if m < self.R:
+            self.raw[m:].zero_()
+        self.raw[:m, :h, :w, :c].copy_(torch.from_numpy(chunk).to(self.raw.device))
+
+    def forward(self, pred, members, what):
+        """The launches of one chunk on the current stream: raw buffer -> views in the staging tensor ->
+        the predictor's forward at ``EB`` rows -> the outputs of ``R`` rows."""
+        job, K = pred.job, pred.K
+        s = job._stream()
+        K.check(job.L.gt_tta_views(self.view_args, s), "tta_views")
+        job._run_fwd(s, pred.ops)
+        K.check(job.L.gt_dense_fwd(pred.df, s), "dense_fwd({})".format(what))
+        K.check(job.L.gt_head_tta(self.heads[bool(members)], s), "head_tta")
+
+
 class HipPredictor(object):
     """Forward-only HIP launches of one fitted model at ``EB`` rows per launch.
 
@@ -379,6 +528,7 @@ class HipPredictor(object):
             hp.logits, hp.proba = self.logits.data_ptr(), self.proba.data_ptr()
             hp.G, hp.B, hp.Up, hp.C = 1, self.EB, job.Up, clf.classes
             self.head = hp
+        self._tta = {}               # views -> TtaState, created on first use
 
     def forward(self):
         """The launches of one chunk on the current stream: staging tensor -> ``logits`` / ``proba``."""
@@ -396,11 +546,34 @@ class HipPredictor(object):
             self.stage[m:].zero_()
         self.stage[:m, :h, :w, :c].copy_(torch.from_numpy(chunk).to(self.device))
 
-    def run(self, x):
-        """``x`` [n, H, W, C] host fp32 -> (logits, proba) host fp32 ``[n, classes]``."""
+    def tta_state(self, views):
+        """The cached :class:`TtaState` of a view tuple: one member of weight 1.0 (``1.0f * p`` is ``p``)."""
+        st = self._tta.get(views)
+        if st is None:
+            with torch.cuda.device(self.device):
+                one = torch.ones(1, dtype=torch.float32, device=self.device)
+                st = self._tta[views] = TtaState(self, views, 1, one)
+        return st
+
+    def run(self, x, views=None):
+        """``x`` [n, H, W, C] host fp32 -> (logits, proba) host fp32 ``[n, classes]``; with ``views`` (a tuple
+        of ``(dy, dx, flip)``) the means over those views of every row, ``EB // len(views)`` rows per launch."""
         n, EB = x.shape[0], self.EB
         logits = torch.empty((n, self.classes), dtype=torch.float32, device=self.device)
         proba = torch.empty_like(logits)
+        if views is not None:
+            st = self.tta_state(tuple(views))
+            R = st.R
+            with torch.cuda.device(self.device):
+                if st.V * R < EB:
+                    self.stage[st.V * R:].zero_()            # rows no view is written to
+                for s in range(0, n, R):
+                    m = min(R, n - s)
+                    st.upload(x[s:s + m], self.hwc)
+                    st.forward(self, True, "predict")
+                    logits[s:s + m].copy_(st.logits[0, :m])
+                    proba[s:s + m].copy_(st.proba[0, :m])
+                return logits.cpu().numpy(), proba.cpu().numpy()
         with torch.cuda.device(self.device):
             for s in range(0, n, EB):
                 m = min(EB, n - s)

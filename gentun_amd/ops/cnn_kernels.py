@@ -170,6 +170,23 @@ class HeadEnsembleArgs(C.Structure):
                 ("G", I), ("B", I), ("Up", I), ("C", I)]
 
 
+class HeadTtaArgs(C.Structure):
+    """csrc/hip/cnn_dense.hip HeadTtaArgs: HeadEnsembleArgs' fields, then the raw rows, the views and fp32
+    1 / views of test-time augmentation (gt_head_tta); the outputs have ``R`` rows."""
+    _fields_ = [("plog", P), ("b2", P), ("weight", P), ("logits", P), ("proba", P), ("ens", P), ("votes", P),
+                ("G", I), ("B", I), ("Up", I), ("C", I), ("R", I), ("V", I), ("inv_v", C.c_float)]
+
+
+TTA_MAXV = 16       # views of one test-time augmentation at most (csrc/hip/cnn_tta.hip TTA_MAXV)
+
+
+class TtaViewArgs(C.Structure):
+    """csrc/hip/cnn_tta.hip TtaViewArgs: the views of a raw chunk into the staging tensor (gt_tta_views)."""
+    _fields_ = [("raw", P), ("out", P), ("R", I), ("V", I), ("rows", I), ("Hp", I), ("Wp", I), ("Hr", I),
+                ("Wr", I), ("Cp", I), ("prec", I), ("dy", I * TTA_MAXV), ("dx", I * TTA_MAXV),
+                ("flip", I * TTA_MAXV)]
+
+
 class DenseDgradArgs(C.Structure):
     _fields_ = [("dH", P), ("wt", P), ("dx", P), ("G", I), ("B", I), ("Fp", I), ("Up", I), ("prec", I),
                 ("wps", C.c_long), ("unpool_mask", P), ("unpool_x0", P), ("unpool_x1", P), ("unpool_sel", P),
@@ -295,6 +312,14 @@ def lib():
         L.gt_head_ensemble.restype = I
         L.gt_sizeof_head_ensemble_args.restype = C.c_size_t
         assert L.gt_sizeof_head_ensemble_args() == C.sizeof(HeadEnsembleArgs), "HeadEnsembleArgs ABI mismatch"
+        L.gt_head_tta.argtypes = [C.POINTER(HeadTtaArgs), P]
+        L.gt_head_tta.restype = I
+        L.gt_sizeof_head_tta_args.restype = C.c_size_t
+        assert L.gt_sizeof_head_tta_args() == C.sizeof(HeadTtaArgs), "HeadTtaArgs ABI mismatch"
+        L.gt_tta_views.argtypes = [C.POINTER(TtaViewArgs), P]
+        L.gt_tta_views.restype = I
+        L.gt_sizeof_tta_view_args.restype = C.c_size_t
+        assert L.gt_sizeof_tta_view_args() == C.sizeof(TtaViewArgs), "TtaViewArgs ABI mismatch"
         L.gt_adam_segments.argtypes = [C.POINTER(AdamArgs), I, P]
         L.gt_adam_segments.restype = I
         L.gt_step_begin.argtypes = [P, P]
