@@ -629,6 +629,71 @@ __global__ void __launch_bounds__(256) head_tta_kernel(HeadTtaArgs a) {
   }
 }
 
+// Occlusion head (models/cnn_fitted.py, models/cnn_ensemble.py): the launch's rows are images of a group of m
+// raw images (phase 0: row r is image r as it is) or their occluded copies (phase 1: row j is item
+// w = w0 + j = r * Cc + cell, gt_occlude_views, cnn_occlude.hip). A row's score vector is the weighted mean
+// of the members' probabilities, as gt_head_ensemble forms it; a single classifier is the ensemble of one
+// member with weight 1.0f (1.0f * p is p), and with `logit` (G == 1 only) its logits take the place of the
+// probabilities.
+struct HeadOcclusionArgs {
+  const float* plog;       // [G][Up/16][B][C] partial logits from dense_fwd (evaluation mode)
+  const float* b2;         // [G][C]
+  const float* weight;     // [G] fp32, normalised on the host
+  int* tgt;                // [m] target class per image; phase 0 replaces a negative entry by the image's label
+  float* base;             // [m] phase 0 writes the unoccluded image's score of its target
+  float* map;              // [m * Cc] phase 1 writes base[r] - score[tgt[r]] of item r * Cc + cell
+  int G, B, Up, C;         // B: the launch's rows (plog's stride)
+  int m, Cc, w0;
+  int phase, logit;
+};
+
+// One workgroup of 4 waves per launch row; wave w runs head_predict_kernel's wave for members w, w + 4, ...
+// (the same helper: every probability and logit is the float gt_head_predict writes for that row) and leaves
+// the member's scores in LDS. After the barrier wave 0 combines the members in member order, exactly as
+// head_ensemble_kernel does, and lane 0 writes the row's one result. Phase 0: the label is the first maximum
+// of the combined probabilities (ascending scan, replaced only on a strict >), whatever `logit` says.
+__global__ void __launch_bounds__(256) head_occlusion_kernel(HeadOcclusionArgs a) {
+  __shared__ float ps[ENS_MAXG][HEAD_MAXC];
+  __shared__ float ls[HEAD_MAXC];                  // the one member's logits (logit mode)
+  const int b = blockIdx.x, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int C = a.C, nt = a.Up / 16;
+  const long w = (long)a.w0 + b;
+  if (a.phase ? w >= (long)a.m * a.Cc : b >= a.m) return;          // block-uniform: no barrier is skipped
+  for (int g = wave; g < a.G; g += 4) {
+    float lo, pr;
+    head_row_softmax(a.plog + ((long)g * nt * a.B + b) * C, a.b2 + (long)g * C, a.B, C, nt, lane, lo, pr);
+    if (lane < C) {
+      ps[g][lane] = pr;
+      if (a.logit) ls[lane] = lo;
+    }
+  }
+  __syncthreads();
+  if (wave != 0) return;
+  const float mean = lane < C ? ensemble_mean(a.weight, ps, a.G, lane) : 0.f;
+  const float score = a.logit ? (lane < C ? ls[lane] : 0.f) : mean;
+  if (a.phase == 0) {
+    int t = a.tgt[b];
+    if (t < 0) {
+      float best = __shfl(mean, 0);
+      t = 0;
+#pragma unroll
+      for (int c = 1; c < HEAD_MAXC; ++c) {
+        const float v = __shfl(mean, c);
+        if (c < C && v > best) { best = v; t = c; }
+      }
+    }
+    const float s = __shfl(score, t);
+    if (lane == 0) {
+      a.tgt[b] = t;
+      a.base[b] = s;
+    }
+  } else {
+    const long r = w / a.Cc;
+    const float s = __shfl(score, a.tgt[r]);
+    if (lane == 0) a.map[w] = a.base[r] - s;
+  }
+}
+
 // (2) grid (ceil(Up/64), G): per 64-unit slice, dH = (dz W2^T) * scale * (h > 0),
 //     gb1 = sum_b dH, gW2 = h^T dz; block 0 also gb2 = sum_b dz.
 __global__ void __launch_bounds__(256) head_bwd_kernel(HeadArgs a) {
@@ -1216,6 +1281,26 @@ int gt_head_tta(const HeadTtaArgs* a, hipStream_t stream) {
   return (int)hipGetLastError();
 }
 
+// Phase 0 launches one workgroup per image (m <= B), phase 1 one per item of [w0, min(w0 + B, m * Cc)).
+int gt_head_occlusion(const HeadOcclusionArgs* a, hipStream_t stream) {
+  if (!a) return -3;
+  if (a->C < 1 || a->C > HEAD_MAXC || a->G < 1 || a->G > ENS_MAXG || a->B < 1) return -1;
+  if (a->Up < 16 || a->Up % 16) return -2;
+  if (!a->plog || !a->b2 || !a->weight || !a->tgt || !a->base) return -3;
+  if (a->m < 1 || a->Cc < 1 || (long)a->m * a->Cc > 0x7fffffffL) return -4;
+  if ((a->phase != 0 && a->phase != 1) || (a->logit != 0 && a->logit != 1)) return -4;
+  if (a->logit && a->G != 1) return -5;
+  long blocks = a->m;
+  if (a->phase == 0) {
+    if (a->m > a->B) return -4;
+  } else {
+    if (!a->map || a->w0 < 0 || a->w0 >= (long)a->m * a->Cc) return -4;
+    blocks = std::min((long)a->B, (long)a->m * a->Cc - a->w0);
+  }
+  hipLaunchKernelGGL(head_occlusion_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, *a);
+  return (int)hipGetLastError();
+}
+
 int gt_dense_dgrad(const DenseDgradArgs* a, hipStream_t stream) {
   if (a->Fp % 64 && a->Fp % 8) return -1;
   if (a->unpool_mask && (a->Cp % 8 || a->Hs % 2 || a->Ws % 2 || (long)(a->Hs / 2) * (a->Ws / 2) * a->Cp != a->Fp))
@@ -1261,6 +1346,7 @@ size_t gt_sizeof_head_args() { return sizeof(HeadArgs); }
 size_t gt_sizeof_head_predict_args() { return sizeof(HeadPredictArgs); }
 size_t gt_sizeof_head_ensemble_args() { return sizeof(HeadEnsembleArgs); }
 size_t gt_sizeof_head_tta_args() { return sizeof(HeadTtaArgs); }
+size_t gt_sizeof_head_occlusion_args() { return sizeof(HeadOcclusionArgs); }
 size_t gt_sizeof_dense_dgrad_args() { return sizeof(DenseDgradArgs); }
 size_t gt_sizeof_dense_wgrad_args() { return sizeof(DenseWgradAdamArgs); }
 

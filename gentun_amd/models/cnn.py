@@ -200,3 +200,10 @@ class GeneticCnnModel(GentunModel):
             raise RuntimeError("GeneticCnnModel.predict before fit()")
         kwargs.setdefault("device", self.device)
         return self.fitted.predict(x, **kwargs)
+
+    def occlusion(self, x, **kwargs):
+        """``self.fitted.occlusion`` on this model's device unless ``device`` says otherwise."""
+        if self.fitted is None:
+            raise RuntimeError("GeneticCnnModel.occlusion before fit()")
+        kwargs.setdefault("device", self.device)
+        return self.fitted.occlusion(x, **kwargs)

@@ -24,7 +24,8 @@ import math
 import numpy as np
 import torch
 
-from .cnn_fitted import CnnClassifier, TtaState, predict_batch, tta_views
+from .cnn_fitted import (CnnClassifier, TtaState, occlusion_by_views, occlusion_fill, occlusion_grid, occlusion_state,
+                         occlusion_targets, predict_batch, tta_views)
 
 FORMAT = "gentun-cnn-ensemble/1"
 OUTPUTS = ("proba", "label", "votes", "vote_label", "member_proba", "member_logits")
@@ -195,6 +196,36 @@ class CnnEnsemble(object):
     def predict_classes(self, x, **kw):
         return self.predict(x, output="label", **kw)
 
+    def occlusion(self, x, target=None, patch=4, stride=None, fill=0.0, score="proba", device=None, batch=256,
+                  backend=None, return_info=False):
+        """Occlusion sensitivity of the ensemble, ``CnnClassifier.occlusion`` with the weighted mean of the
+        members' probabilities (``"proba"`` of :meth:`predict`) as the score: fp32 ``[n, Gh, Gw]``, the score of
+        the target class minus its score with the cell replaced by ``fill``. ``target=None``: the first maximum
+        of the weighted mean of the unoccluded image. The members' logits have no weighted mean here:
+        ``score="logit"`` raises ``ValueError``."""
+        if score != "proba":
+            raise ValueError("score {!r}: an ensemble's occlusion score is 'proba'".format(score))
+        if int(batch) < 1:
+            raise ValueError("batch must be positive")
+        x = self.members[0]._check_x(x)
+        occlusion_grid(self.input_shape, patch, stride)
+        fill = occlusion_fill(fill, self.input_shape[2])
+        target = occlusion_targets(target, x.shape[0], self.classes)
+        dev = torch.device("cpu" if device is None else device)
+        if backend is None:
+            backend = "hip" if dev.type == "cuda" else "torch"
+        if backend == "hip":
+            res = self.hip_predictor(dev, batch).occlusion(x, target, patch, stride, fill)
+        elif backend == "torch":
+            def scores(images):
+                member = np.stack([m._torch_predict(images, dev, int(batch), torch.float32)[1] for m in self.members])
+                proba = combine(member, self.weights)[0]
+                return proba, proba
+            res = occlusion_by_views(scores, x, target, patch, stride, fill, int(batch))
+        else:
+            raise ValueError("unknown backend {!r}".format(backend))
+        return (res[0], {"target": res[1], "base": res[2]}) if return_info else res[0]
+
     def hip_predictor(self, device, batch=256):
         """The cached :class:`HipEnsemblePredictor` of (device, rows per launch). The rows per launch are
         ``predict_batch(batch)`` lowered by the executor's rule for evaluation twins (``EVAL_TWIN_BUDGET``
@@ -265,6 +296,7 @@ class HipEnsemblePredictor(object):
                 a.G, a.B, a.Up, a.C = k, EB, job.Up, C
                 self.heads[members] = a
         self._tta = {}               # views -> TtaState, created on first use
+        self._occ = {}               # (patch, stride, fill, score) -> OcclusionState, created on first use
 
     def _host(self, ens, EB):
         from . import cnn_engine as E
@@ -307,6 +339,11 @@ class HipEnsemblePredictor(object):
             with torch.cuda.device(self.device):
                 st = self._tta[views] = TtaState(self, views, self.k, self.weight)
         return st
+
+    def occlusion(self, x, target, patch, stride, fill):
+        """``(map, target, base)`` of validated arguments (``CnnEnsemble.occlusion``) over the ``k`` members and
+        their weights."""
+        return occlusion_state(self, patch, stride, fill, "proba", self.k, self.weight).run(self, x, target)
 
     def run(self, x, members=False, views=None):
         """``x`` [n, H, W, C] host fp32 -> ``{"proba", "votes"}`` (+ ``"member_proba"``, ``"member_logits"``)

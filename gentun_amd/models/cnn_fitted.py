@@ -109,6 +109,110 @@ def tta_combine(per_view):
     return (acc * (one(1) / one(len(per_view)))).astype(acc.dtype, copy=False)
 
 
+OCC_MAX_CELLS = 4096         # OCC_MAX_CELLS of csrc/hip/cnn_occlude.hip
+OCC_SCORES = ("proba", "logit")
+
+
+def occlusion_grid(input_shape, patch, stride=None):
+    """``(Gh, Gw)``, the grid of an occlusion request over images of ``input_shape`` ``(H, W, C)``.
+
+    ``patch`` is an int with ``1 <= patch <= min(H, W)``; ``stride`` an int with ``1 <= stride <= patch`` (every
+    pixel is covered) or ``None`` for ``patch``. ``Gh = ceil((H - patch) / stride) + 1`` and ``Gw`` likewise, at
+    most ``OCC_MAX_CELLS`` cells together. Cell ``(gi, gj)``, of flat index ``gi * Gw + gj``, covers the rows
+    ``[gi * stride, min(gi * stride + patch, H))`` and the columns likewise: the last window is clipped, not
+    moved. ``ValueError`` on anything else."""
+    H, W = int(input_shape[0]), int(input_shape[1])
+    if stride is None:
+        stride = patch
+    if not _is_int(patch) or not _is_int(stride):
+        raise ValueError("occlusion: patch and stride must be integers, got {!r} and {!r}".format(patch, stride))
+    patch, stride = int(patch), int(stride)
+    if not 1 <= patch <= min(H, W):
+        raise ValueError("occlusion: patch {} must be in [1, min(H, W) = {}]".format(patch, min(H, W)))
+    if not 1 <= stride <= patch:
+        raise ValueError("occlusion: stride {} must be in [1, patch = {}]".format(stride, patch))
+    Gh, Gw = -(-(H - patch) // stride) + 1, -(-(W - patch) // stride) + 1
+    if Gh * Gw > OCC_MAX_CELLS:
+        raise ValueError("occlusion: {} x {} cells, at most {}".format(Gh, Gw, OCC_MAX_CELLS))
+    return Gh, Gw
+
+
+def occlusion_fill(fill, channels):
+    """``fill`` (a number or ``channels`` numbers, finite) as an fp32 array ``[channels]``."""
+    try:
+        f = np.asarray(fill, np.float64)
+    except (TypeError, ValueError):
+        raise ValueError("occlusion: fill must be a number or {} numbers, got {!r}".format(channels, fill))
+    if f.ndim == 0:
+        f = np.full(channels, float(f))
+    if f.shape != (channels,) or not np.isfinite(f).all():
+        raise ValueError("occlusion: fill must be a finite number or {} of them, got {!r}".format(channels, fill))
+    return f.astype(np.float32)
+
+
+def occlusion_views(x, patch, stride=None, fill=0.0):
+    """The occluded copies ``[n, Gh * Gw, H, W, C]`` of images ``x [n, H, W, C]``: copy ``gi * Gw + gj`` of an
+    image has ``fill[c]`` inside cell ``(gi, gj)`` of :func:`occlusion_grid` and the image elsewhere. Slicing
+    only; ``fill`` is rounded to the dtype of ``x``."""
+    n, H, W, C = x.shape
+    Gh, Gw = occlusion_grid((H, W, C), patch, stride)
+    stride = int(patch if stride is None else stride)
+    f = occlusion_fill(fill, C).astype(x.dtype)
+    out = np.repeat(x[:, None], Gh * Gw, axis=1)
+    for gi in range(Gh):
+        for gj in range(Gw):
+            out[:, gi * Gw + gj, gi * stride:gi * stride + int(patch), gj * stride:gj * stride + int(patch)] = f
+    return out
+
+
+def occlusion_targets(target, n, classes):
+    """``target`` of an occlusion request as ``None`` (the model's own label of every image) or int64 ``[n]``
+    from one class index or ``n`` of them in ``[0, classes)``."""
+    if target is None:
+        return None
+    t = np.asarray(target)
+    if t.dtype == np.bool_ or not np.issubdtype(t.dtype, np.integer) or t.ndim > 1:
+        raise ValueError("occlusion: target must be None, a class index or one class index per image")
+    t = np.full(n, int(t), np.int64) if t.ndim == 0 else t.astype(np.int64)
+    if t.shape != (n,):
+        raise ValueError("occlusion: {} targets for {} images".format(t.shape[0], n))
+    if n and (t.min() < 0 or t.max() >= classes):
+        raise ValueError("occlusion: targets must be in [0, {})".format(classes))
+    return t
+
+
+def occlusion_by_views(scores, x, target, patch, stride, fill, batch, rows=4096):
+    """The occlusion map by :func:`occlusion_views`: ``scores(images [k, H, W, C])`` returns ``(score, proba)``,
+    fp32 ``[k, classes]`` each, ``batch`` rows per forward -- the score vectors to difference and the
+    probabilities whose first maximum is the label. Returns ``(map [n, Gh, Gw], target int64 [n], base fp32 [n])``
+    with ``map[r, gi, gj] = score(x[r])[t_r] - score(O_cell(x[r]))[t_r]``, one fp32 subtraction.
+
+    The copies of all images form one sequence of ``n * Gh * Gw`` rows; it is produced a few images at a time
+    and scored in pieces of a multiple of ``batch`` rows (about ``rows``), so every forward holds the rows it
+    would hold if the whole sequence were given to ``scores`` at once."""
+    n = x.shape[0]
+    Gh, Gw = occlusion_grid(x.shape[1:], patch, stride)
+    Cc = Gh * Gw
+    sc, pr = scores(x)
+    tgt = np.argmax(pr, axis=1).astype(np.int64) if target is None else target
+    base = np.asarray(sc, np.float32)[np.arange(n), tgt]
+    piece = int(batch) * max(1, int(rows) // int(batch))
+    step = max(1, piece // Cc)
+    wanted = np.repeat(tgt, Cc)                          # the class to keep of every row of the sequence
+    occluded = np.empty(n * Cc, np.float32)
+    pending, done = np.empty((0,) + x.shape[1:], np.float32), 0
+    for s in range(0, n, step):
+        views = occlusion_views(x[s:s + step], patch, stride, fill)
+        pending = np.concatenate([pending, views.reshape((-1,) + x.shape[1:])])
+        last = s + step >= n
+        while len(pending) >= piece or (last and len(pending)):
+            k = min(piece, len(pending))
+            sv = np.asarray(scores(pending[:k])[0], np.float32)
+            occluded[done:done + k] = sv[np.arange(k), wanted[done:done + k]]
+            pending, done = pending[k:], done + k
+    return (np.repeat(base, Cc) - occluded).reshape(n, Gh, Gw), tgt, base
+
+
 def predict_batch(batch):
     """Rows per launch of the HIP predictor: ``batch`` rounded up to a multiple of 32, at least 32 and
     at most 256 (the cap of ``HipPopJob.eval_batch``)."""
@@ -261,6 +365,44 @@ class CnnClassifier(object):
 
     def predict_classes(self, x, **kw):
         return self.predict(x, output="label", **kw)
+
+    def occlusion(self, x, target=None, patch=4, stride=None, fill=0.0, score="proba", device=None, batch=256,
+                  backend=None, return_info=False):
+        """Occlusion sensitivity (Zeiler & Fergus) of ``x`` ``[n, H, W, C]`` (or one image): fp32
+        ``[n, Gh, Gw]`` with ``map[r, gi, gj] = s(x[r]) - s(O_cell(x[r]))``, one fp32 subtraction, where
+        ``O_cell`` replaces cell ``(gi, gj)`` of :func:`occlusion_grid` by ``fill`` (a number or one per channel)
+        and ``s`` is the probability (``score="proba"``) or the logit (``"logit"``) of the target class. Positive:
+        the region supports the class.
+
+        ``target``: ``None`` for the model's own label of the unoccluded image (the first maximum of the
+        probabilities), one class index, or one per image. ``return_info=True`` returns
+        ``(map, {"target": int64 [n], "base": fp32 [n]})``, the classes used and ``s(x[r])``.
+
+        ``device`` / ``backend`` / ``batch`` as in :meth:`predict`: the CPU or ``backend="torch"`` feeds
+        :func:`occlusion_views` to the stock-torch forward and subtracts in numpy; a ``cuda`` device uploads every
+        image once, builds the occluded copies on the device (``gt_occlude_views``), packs them densely into
+        launches of ``EB`` rows and keeps one float per copy (``gt_head_occlusion``)."""
+        if score not in OCC_SCORES:
+            raise ValueError("score {!r}: expected one of {}".format(score, OCC_SCORES))
+        if int(batch) < 1:
+            raise ValueError("batch must be positive")
+        x = self._check_x(x)
+        occlusion_grid(self.input_shape, patch, stride)
+        fill = occlusion_fill(fill, self.input_shape[2])
+        target = occlusion_targets(target, x.shape[0], self.classes)
+        dev = torch.device("cpu" if device is None else device)
+        if backend is None:
+            backend = "hip" if dev.type == "cuda" else "torch"
+        if backend == "hip":
+            res = self.hip_predictor(dev, batch).occlusion(x, target, patch, stride, fill, score)
+        elif backend == "torch":
+            def scores(images):
+                logits, proba = self._torch_predict(images, dev, int(batch), torch.float32)
+                return (logits if score == "logit" else proba), proba
+            res = occlusion_by_views(scores, x, target, patch, stride, fill, int(batch))
+        else:
+            raise ValueError("unknown backend {!r}".format(backend))
+        return (res[0], {"target": res[1], "base": res[2]}) if return_info else res[0]
 
     def hip_predictor(self, device, batch=256):
         """The cached :class:`HipPredictor` of (device, rows per launch)."""
@@ -482,6 +624,105 @@ class TtaState(object):
         K.check(job.L.gt_head_tta(self.heads[bool(members)], s), "head_tta")
 
 
+class OcclusionState(object):
+    """What a HIP predictor (``HipPredictor`` or ``HipEnsemblePredictor``) adds for one occlusion setting
+    ``(patch, stride, fill, score)``: the raw buffer of up to ``EB`` images in the staging tensor's layout and
+    element type (zero outside the real extent and in the channel padding), the fill value in that type, the
+    arguments of ``gt_occlude_views`` (raw buffer -> the launch's items in the staging tensor) and of
+    ``gt_head_occlusion`` (phase 0: target and base score per image; phase 1: one map element per launch row)
+    and the results of one group. The unit of work is the item ``w = r * Cc + cell``; items are packed densely
+    into launches of ``EB`` rows. The predictor's job, evaluation launches and gather table are used as they
+    are, at ``EB`` rows."""
+
+    def __init__(self, pred, patch, stride, fill, score, G, weight):
+        K, job, stage = pred.K, pred.job, pred.stage
+        h, w, c = pred.hwc
+        self.Gh, self.Gw = occlusion_grid(pred.hwc, patch, stride)
+        self.Cc = Cc = self.Gh * self.Gw
+        EB, dev = pred.EB, pred.device
+        self.raw = torch.zeros((EB,) + tuple(stage.shape[1:]), dtype=stage.dtype, device=dev)
+        f = torch.zeros(int(stage.shape[3]), dtype=torch.float32)
+        f[:c] = torch.from_numpy(occlusion_fill(fill, c))
+        self.fill = f.to(stage.dtype).to(dev)            # rounded to the staging type on the host
+        self.weight = weight
+        self.tgt = torch.empty(EB, dtype=torch.int32, device=dev)
+        self.base = torch.empty(EB, dtype=torch.float32, device=dev)
+        self.map = torch.empty(EB * Cc, dtype=torch.float32, device=dev)
+        va = K.OccludeArgs()
+        va.raw, va.out, va.fill = self.raw.data_ptr(), stage.data_ptr(), self.fill.data_ptr()
+        va.Cc, va.Gw, va.patch = Cc, self.Gw, int(patch)
+        va.stride = int(patch if stride is None else stride)
+        va.rows = va.cap = EB
+        va.Hp, va.Wp, va.Cp = (int(d) for d in stage.shape[1:])
+        va.Hr, va.Wr = h, w
+        va.prec = 1 if stage.dtype == torch.float32 else 0
+        self.view_args = va
+        a = K.HeadOcclusionArgs()
+        a.plog, a.b2, a.weight = pred.df.plog, job.views["b2"][0].data_ptr(), weight.data_ptr()
+        a.tgt, a.base, a.map = self.tgt.data_ptr(), self.base.data_ptr(), self.map.data_ptr()
+        a.G, a.B, a.Up, a.C = G, EB, job.Up, pred.classes
+        a.Cc, a.logit = Cc, 1 if score == "logit" else 0
+        self.head = a
+
+    def upload(self, chunk, target, hwc):
+        """``chunk`` [m <= EB, H, W, C] host fp32 into the raw buffer (rows past ``m`` become zero images) and
+        its targets (int64 ``[m]``, or ``None``: -1, the label) into ``tgt``."""
+        m = chunk.shape[0]
+        h, w, c = hwc
+        if m < self.raw.shape[0]:
+            self.raw[m:].zero_()
+        self.raw[:m, :h, :w, :c].copy_(torch.from_numpy(chunk).to(self.raw.device))
+        if target is None:
+            self.tgt.fill_(-1)
+        else:
+            self.tgt[:m].copy_(torch.from_numpy(target.astype(np.int32)).to(self.tgt.device))
+
+    def launch(self, pred, m, w0, base):
+        """One launch set on the current stream: the items from ``w0`` (``base``: the ``m`` images as they are)
+        -> the staging tensor -> the predictor's forward at ``EB`` rows -> ``tgt`` / ``base`` or ``map``."""
+        job, K = pred.job, pred.K
+        s = job._stream()
+        va, a = self.view_args, self.head
+        va.m, va.w0, va.base = m, w0, 1 if base else 0
+        a.m, a.w0, a.phase = m, w0, 0 if base else 1
+        K.check(job.L.gt_occlude_views(va, s), "occlude_views")
+        job._run_fwd(s, pred.ops)
+        K.check(job.L.gt_dense_fwd(pred.df, s), "dense_fwd(occlusion)")
+        K.check(job.L.gt_head_occlusion(a, s), "head_occlusion")
+
+    def run(self, pred, x, target):
+        """``x`` [n, H, W, C] host fp32 -> ``(map [n, Gh, Gw], target int64 [n], base fp32 [n])`` as host
+        arrays: per group of ``EB`` images one upload, one base launch and ``ceil(m * Cc / EB)`` packed launches;
+        the results gather on the device and are read back once."""
+        n, EB, Cc, dev = x.shape[0], pred.EB, self.Cc, pred.device
+        with torch.cuda.device(dev):
+            out = torch.empty(n * Cc, dtype=torch.float32, device=dev)
+            tgt = torch.empty(n, dtype=torch.int32, device=dev)
+            base = torch.empty(n, dtype=torch.float32, device=dev)
+            for s in range(0, n, EB):
+                m = min(EB, n - s)
+                self.upload(x[s:s + m], None if target is None else target[s:s + m], pred.hwc)
+                self.launch(pred, m, 0, True)
+                for w0 in range(0, m * Cc, EB):
+                    self.launch(pred, m, w0, False)
+                out[s * Cc:(s + m) * Cc].copy_(self.map[:m * Cc])
+                tgt[s:s + m].copy_(self.tgt[:m])
+                base[s:s + m].copy_(self.base[:m])
+            return (out.cpu().numpy().reshape(n, self.Gh, self.Gw), tgt.cpu().numpy().astype(np.int64),
+                    base.cpu().numpy())
+
+
+def occlusion_state(pred, patch, stride, fill, score, G, weight):
+    """The cached :class:`OcclusionState` of a predictor (its ``_occ`` dict) for one setting."""
+    stride = int(patch if stride is None else stride)
+    key = (int(patch), stride, tuple(float(v) for v in fill), score)
+    st = pred._occ.get(key)
+    if st is None:
+        with torch.cuda.device(pred.device):
+            st = pred._occ[key] = OcclusionState(pred, int(patch), stride, fill, score, G, weight)
+    return st
+
+
 class HipPredictor(object):
     """Forward-only HIP launches of one fitted model at ``EB`` rows per launch.
 
@@ -529,6 +770,8 @@ class HipPredictor(object):
             hp.G, hp.B, hp.Up, hp.C = 1, self.EB, job.Up, clf.classes
             self.head = hp
         self._tta = {}               # views -> TtaState, created on first use
+        self._occ = {}               # (patch, stride, fill, score) -> OcclusionState, created on first use
+        self._one = None             # the one member's weight 1.0 on the device, for the occlusion head
 
     def forward(self):
         """The launches of one chunk on the current stream: staging tensor -> ``logits`` / ``proba``."""
@@ -554,6 +797,13 @@ class HipPredictor(object):
                 one = torch.ones(1, dtype=torch.float32, device=self.device)
                 st = self._tta[views] = TtaState(self, views, 1, one)
         return st
+
+    def occlusion(self, x, target, patch, stride, fill, score):
+        """``(map, target, base)`` of validated arguments (``CnnClassifier.occlusion``): one member of weight
+        1.0 (``1.0f * p`` is ``p``)."""
+        if self._one is None:
+            self._one = torch.ones(1, dtype=torch.float32, device=self.device)
+        return occlusion_state(self, patch, stride, fill, score, 1, self._one).run(self, x, target)
 
     def run(self, x, views=None):
         """``x`` [n, H, W, C] host fp32 -> (logits, proba) host fp32 ``[n, classes]``; with ``views`` (a tuple

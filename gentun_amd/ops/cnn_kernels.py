@@ -187,6 +187,24 @@ class TtaViewArgs(C.Structure):
                 ("flip", I * TTA_MAXV)]
 
 
+class HeadOcclusionArgs(C.Structure):
+    """csrc/hip/cnn_dense.hip HeadOcclusionArgs: the target and base score of every image (phase 0), then one
+    element of the occlusion map per launch row (phase 1) (gt_head_occlusion)."""
+    _fields_ = [("plog", P), ("b2", P), ("weight", P), ("tgt", P), ("base", P), ("map", P),
+                ("G", I), ("B", I), ("Up", I), ("C", I), ("m", I), ("Cc", I), ("w0", I), ("phase", I), ("logit", I)]
+
+
+OCC_MAX_CELLS = 4096    # cells of one occlusion grid at most (csrc/hip/cnn_occlude.hip OCC_MAX_CELLS)
+
+
+class OccludeArgs(C.Structure):
+    """csrc/hip/cnn_occlude.hip OccludeArgs: the occluded copies of a group of raw images, packed item by item
+    into the staging tensor (gt_occlude_views)."""
+    _fields_ = [("raw", P), ("out", P), ("fill", P), ("m", I), ("w0", I), ("Cc", I), ("Gw", I), ("patch", I),
+                ("stride", I), ("rows", I), ("cap", I), ("Hp", I), ("Wp", I), ("Hr", I), ("Wr", I), ("Cp", I),
+                ("prec", I), ("base", I)]
+
+
 class DenseDgradArgs(C.Structure):
     _fields_ = [("dH", P), ("wt", P), ("dx", P), ("G", I), ("B", I), ("Fp", I), ("Up", I), ("prec", I),
                 ("wps", C.c_long), ("unpool_mask", P), ("unpool_x0", P), ("unpool_x1", P), ("unpool_sel", P),
@@ -320,6 +338,15 @@ def lib():
         L.gt_tta_views.restype = I
         L.gt_sizeof_tta_view_args.restype = C.c_size_t
         assert L.gt_sizeof_tta_view_args() == C.sizeof(TtaViewArgs), "TtaViewArgs ABI mismatch"
+        L.gt_head_occlusion.argtypes = [C.POINTER(HeadOcclusionArgs), P]
+        L.gt_head_occlusion.restype = I
+        L.gt_sizeof_head_occlusion_args.restype = C.c_size_t
+        assert L.gt_sizeof_head_occlusion_args() == C.sizeof(HeadOcclusionArgs), "HeadOcclusionArgs ABI mismatch"
+        L.gt_occlude_views.argtypes = [C.POINTER(OccludeArgs), P]
+        L.gt_occlude_views.restype = I
+        L.gt_sizeof_occlude_args.restype = C.c_size_t
+        assert L.gt_sizeof_occlude_args() == C.sizeof(OccludeArgs), "OccludeArgs ABI mismatch"
+        assert L.gt_occlude_max_cells() == OCC_MAX_CELLS, "OCC_MAX_CELLS mismatch"
         L.gt_adam_segments.argtypes = [C.POINTER(AdamArgs), I, P]
         L.gt_adam_segments.restype = I
         L.gt_step_begin.argtypes = [P, P]

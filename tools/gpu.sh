@@ -19,6 +19,7 @@
 #   bash tools/gpu.sh cnn-ensemble            CnnEnsemble.predict: one k-group launch set vs k predictors one by one vs stock torch; fit_ensemble vs k fits (ROWS= REPS= K= FIT_ROWS=)
 #   bash tools/gpu.sh cnn-augment             TrainConfig.augment: step time off / on (and the parent tree in ab_old/), gt_augment's kernel time (GROUPS_LIST= REPS= PROF_GROUPS= OUT=)
 #   bash tools/gpu.sh cnn-tta                 predict(tta=...): views and mean on the device vs V plain HIP predicts combined in numpy vs stock torch, classifier and k-ensemble (ROWS= FIT_ROWS= K= REPS= OUT=)
+#   bash tools/gpu.sh cnn-occlusion           occlusion(): copies built and packed on the device vs occlusion_views in numpy + plain HIP predicts vs stock torch, classifier and k-ensemble (ROWS= FIT_ROWS= K= REPS= OUT= TIME=)
 #   bash tools/gpu.sh rehearse                2-rank torchrun bench on one GPU (gloo control plane)
 #   bash tools/gpu.sh secondary               bench lines: reference fold semantics, torch comparator
 #
@@ -191,6 +192,13 @@ cnn-tta)
     --k ${K:-4} --reps ${REPS:-5} ${TTA_ARGS:-} > $out/bench.json 2> $out/bench.err; rc=$?
   [ $rc -eq 0 ] && cut -c1-6000 $out/bench.json || tail -5 $out/bench.err
   exit $rc ;;
+cnn-occlusion)
+  # one line per finished case, then the result line; the files are kept under $OUT
+  out=${OUT:-/tmp/cnn_occlusion}; heartbeat; mkdir -p $out
+  timeout -k 10 ${TIME:-900} python -u tools/bench_cnn_occlusion.py --rows ${ROWS:-1000} --fit-rows ${FIT_ROWS:-2000} \
+    --k ${K:-4} --reps ${REPS:-5} ${OCC_ARGS:-} > $out/bench.json 2> $out/bench.err; rc=$?
+  [ $rc -eq 0 ] && tail -1 $out/bench.json | cut -c1-8000 || { tail -5 $out/bench.err; cut -c1-2000 $out/bench.json; }
+  exit $rc ;;
 rehearse)
   heartbeat
   GENTUN_DIST_BACKEND=gloo timeout -k 10 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node ${N:-2} \
@@ -212,5 +220,5 @@ secondary)
     cat gpurun_out/sec/torch.json
   fi ;;
 *)
-  sed -n 2,23p "$0"; exit 2 ;;
+  sed -n 2,24p "$0"; exit 2 ;;
 esac
