@@ -694,6 +694,184 @@ __global__ void __launch_bounds__(256) head_occlusion_kernel(HeadOcclusionArgs a
   }
 }
 
+// Grad-CAM (models/cnn_fitted.py, models/cnn_ensemble.py) at the network's last feature map A[c][i][j], the
+// pooled map dense_fwd reads as [hs][ws][Cp] features. The score's gradient passes through the dense head only,
+// and the channel weight alpha[c] = mean_{i,j} dS/dA[c][i][j] = (1 / (hr * wr)) * sum_u dH[u] * wbar[c][u] needs
+// W1 only through wbar[c][u] = sum_{i,j} W1[(i, j, c)][u], a constant of the fitted model: no data-gradient
+// GEMM is launched.
+struct CamW1SumArgs {
+  const float* w1;         // [G][hs * ws * Cp][Up] the fp32 master of W1
+  float* wbar;             // [G][Cp][Up]
+  int G, hs, ws, hr, wr;   // stored and real pixels of the last feature map
+  int Cp, Cr, Up;          // stored and real channels
+};
+
+#define CAM_MAXU 4096
+#define CAM_MAXC 256
+#define CAM_MAXPX 1024
+
+// One thread per (c, u), u fastest (coalesced rows of W1); plain fp32 adds over the real pixels in row-major
+// order. Rows of padded pixels are never read; channels >= Cr write 0.
+__global__ void __launch_bounds__(256) cam_w1sum_kernel(CamW1SumArgs a) {
+  const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= (long)a.Cp * a.Up) return;
+  const int g = blockIdx.y, c = (int)(idx / a.Up), u = (int)(idx % a.Up);
+  float acc = 0.f;
+  if (c < a.Cr) {
+    const float* w = a.w1 + (long)g * a.hs * a.ws * a.Cp * a.Up + (long)c * a.Up + u;
+    for (int i = 0; i < a.hr; ++i)
+      for (int j = 0; j < a.wr; ++j) acc = acc + w[(long)(i * a.ws + j) * a.Cp * a.Up];
+  }
+  a.wbar[((long)g * a.Cp + c) * a.Up + u] = acc;
+}
+
+struct HeadGradcamArgs {
+  const float* plog;       // [G][Up/16][B][C] partial logits from dense_fwd (evaluation mode)
+  const float* b2;         // [G][C]
+  const float* weight;     // [G] fp32, normalised on the host
+  const void* feat;        // [G][B][hs * ws * Cp] dense_fwd's input, bf16 or fp32 (prec)
+  const void* hid;         // [G][B][Up] dense_fwd's output h = relu(z), bf16 or fp32 (prec)
+  const float* w2;         // [G][Up][C]
+  const float* wbar;       // [G][Cp][Up] from gt_cam_w1sum
+  int* tgt;                // [m] target class per image; a negative entry is replaced by the image's label
+  float* base;             // [m] the score of the target
+  float* map;              // [m][hr][wr]
+  int G, B, Up, C;         // B: the launch's rows (the stride of plog, feat and hid)
+  int m, hs, ws, hr, wr, Cp, Cr;
+  int prec, logit, relu;
+  float inv_n;             // fp32(1) / fp32(hr * wr), from the host
+};
+
+template <int PREC>
+__device__ __forceinline__ float cam_ld(const void* p, long i) {
+  if (PREC) return static_cast<const float*>(p)[i];
+  return bf2f(static_cast<const uint16_t*>(p)[i]);
+}
+
+// One workgroup of 4 waves per image b < m.
+// (a) head_occlusion_kernel's phase 0: every member's softmax by head_row_softmax, then wave 0 forms the label
+//     (first maximum of the combined probabilities) and the base score -- the weighted mean, in member order,
+//     of the members' probabilities (or, with `logit`, logits) of the target.
+// Then per member g, every sum in one fixed order with the multiply and the add rounded separately:
+// (b) coef[c] = [c == t] (logit) or p[t] * ([c == t] - p[c]) (probability), and one thread per unit u:
+//     dH[u] = h[u] > 0 ? sum_c coef[c] * W2[u][c] : 0, classes ascending (h > 0 is read off the bits: a positive
+//     sign and any non-zero magnitude, the smallest subnormal included, whatever the denormal mode);
+// (c) one wave per channel c < Cr: lane l sums dH[u] * wbar[c][u] over u = l, l + 64, ... ascending, then the
+//     xor tree 32..1 of head_row_softmax, then * inv_n;
+// (d) one thread per real pixel: cam = sum_{c < Cr} alpha[c] * A[c][i][j], channels ascending; ReLU if asked;
+// (e) map = w[0] * cam_0, then map + w[g] * cam_g: ensemble_mean's rounding.
+template <int PREC>
+__global__ void __launch_bounds__(256) head_gradcam_kernel(HeadGradcamArgs a) {
+#pragma clang fp contract(off)
+  __shared__ float ps[ENS_MAXG][HEAD_MAXC];
+  __shared__ float ls[ENS_MAXG][HEAD_MAXC];
+  __shared__ float dh[CAM_MAXU];
+  __shared__ float alpha[CAM_MAXC];
+  __shared__ float coef[HEAD_MAXC];
+  __shared__ int tsh;
+  const int b = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int C = a.C, nt = a.Up / 16, npx = a.hr * a.wr;
+  if (b >= a.m) return;                            // block-uniform: no barrier is skipped
+  for (int g = wave; g < a.G; g += 4) {
+    float lo, pr;
+    head_row_softmax(a.plog + ((long)g * nt * a.B + b) * C, a.b2 + (long)g * C, a.B, C, nt, lane, lo, pr);
+    if (lane < C) {
+      ps[g][lane] = pr;
+      ls[g][lane] = lo;
+    }
+  }
+  __syncthreads();
+  if (wave == 0) {
+    const float mean = lane < C ? ensemble_mean(a.weight, ps, a.G, lane) : 0.f;
+    const float score = a.logit ? (lane < C ? ensemble_mean(a.weight, ls, a.G, lane) : 0.f) : mean;
+    int t = a.tgt[b];
+    if (t < 0) {
+      float best = __shfl(mean, 0);
+      t = 0;
+#pragma unroll
+      for (int c = 1; c < HEAD_MAXC; ++c) {
+        const float v = __shfl(mean, c);
+        if (c < C && v > best) { best = v; t = c; }
+      }
+    }
+    // the host guarantees a given target t < C (occlusion_targets raises otherwise) and the launcher cannot see
+    // device memory, so nothing refuses one; the clamp only keeps such a target from indexing past the tables
+    t = min(t, C - 1);
+    const float s = __shfl(score, t);
+    if (lane == 0) {
+      a.tgt[b] = t;
+      a.base[b] = s;
+      tsh = t;
+    }
+  }
+  __syncthreads();
+  const int t = tsh;
+  float acc[CAM_MAXPX / 256];
+#pragma unroll
+  for (int k = 0; k < CAM_MAXPX / 256; ++k) acc[k] = 0.f;
+  for (int g = 0; g < a.G; ++g) {
+    if (tid < C) {
+      const float hot = tid == t ? 1.f : 0.f;
+      float cf = hot;
+      if (!a.logit) {
+        const float d = hot - ps[g][tid];
+        cf = ps[g][t] * d;
+      }
+      coef[tid] = cf;
+    }
+    __syncthreads();
+    for (int u = tid; u < a.Up; u += 256) {
+      const float h = cam_ld<PREC>(a.hid, ((long)g * a.B + b) * a.Up + u);
+      float v = 0.f;
+      if (__float_as_int(h) > 0) {
+        const float* w2 = a.w2 + ((long)g * a.Up + u) * C;
+        v = coef[0] * w2[0];
+        for (int c = 1; c < C; ++c) {
+          const float term = coef[c] * w2[c];
+          v = v + term;
+        }
+      }
+      dh[u] = v;
+    }
+    __syncthreads();
+    for (int c = wave; c < a.Cr; c += 4) {
+      const float* wb = a.wbar + ((long)g * a.Cp + c) * a.Up;
+      float s = 0.f;
+      for (int u = lane; u < a.Up; u += 64) {
+        const float term = dh[u] * wb[u];
+        s = s + term;
+      }
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) s = s + __shfl_xor(s, o);
+      if (lane == 0) alpha[c] = s * a.inv_n;
+    }
+    __syncthreads();
+    const float wg = a.weight[g];
+    const long f0 = ((long)g * a.B + b) * a.hs * a.ws * a.Cp;
+#pragma unroll
+    for (int k = 0; k < CAM_MAXPX / 256; ++k) {
+      const int p = tid + k * 256;
+      if (p < npx) {
+        const long px = f0 + (long)((p / a.wr) * a.ws + p % a.wr) * a.Cp;
+        float v = 0.f;
+        for (int c = 0; c < a.Cr; ++c) {
+          const float term = alpha[c] * cam_ld<PREC>(a.feat, px + c);
+          v = v + term;
+        }
+        if (a.relu) v = v > 0.f ? v : 0.f;
+        const float term = wg * v;
+        acc[k] = g == 0 ? term : acc[k] + term;
+      }
+    }
+    // the next member's coef / dh / alpha writes each follow a barrier that every reader here has passed
+  }
+#pragma unroll
+  for (int k = 0; k < CAM_MAXPX / 256; ++k) {
+    const int p = tid + k * 256;
+    if (p < npx) a.map[(long)b * npx + p] = acc[k];
+  }
+}
+
 // (2) grid (ceil(Up/64), G): per 64-unit slice, dH = (dz W2^T) * scale * (h > 0),
 //     gb1 = sum_b dH, gW2 = h^T dz; block 0 also gb2 = sum_b dz.
 __global__ void __launch_bounds__(256) head_bwd_kernel(HeadArgs a) {
@@ -1301,6 +1479,41 @@ int gt_head_occlusion(const HeadOcclusionArgs* a, hipStream_t stream) {
   return (int)hipGetLastError();
 }
 
+static bool cam_geometry_ok(int G, int hs, int ws, int hr, int wr, int Cp, int Cr, int Up) {
+  if (G < 1 || G > ENS_MAXG) return false;
+  if (Up < 16 || Up % 16 || Up > CAM_MAXU) return false;
+  if (Cp < 8 || Cp % 8 || Cp > CAM_MAXC || Cr < 1 || Cr > Cp) return false;
+  if (hr < 1 || wr < 1 || hr > hs || wr > ws || hs > 0x7fff || ws > 0x7fff) return false;
+  if ((long)hr * wr > CAM_MAXPX) return false;
+  return (long)G * hs * ws * Cp * Up <= 0x7fffffffffffL / 4;
+}
+
+// One thread per (c, u) of every group.
+int gt_cam_w1sum(const CamW1SumArgs* a, hipStream_t stream) {
+  if (!a || !a->w1 || !a->wbar) return -3;
+  if (!cam_geometry_ok(a->G, a->hs, a->ws, a->hr, a->wr, a->Cp, a->Cr, a->Up)) return -1;
+  const unsigned blocks = (unsigned)(((long)a->Cp * a->Up + 255) / 256);
+  hipLaunchKernelGGL(cam_w1sum_kernel, dim3(blocks, (unsigned)a->G), dim3(256), 0, stream, *a);
+  return (int)hipGetLastError();
+}
+
+// One workgroup per image of the launch's first m rows.
+int gt_head_gradcam(const HeadGradcamArgs* a, hipStream_t stream) {
+  if (!a) return -3;
+  if (a->C < 1 || a->C > HEAD_MAXC || a->B < 1) return -1;
+  if (!cam_geometry_ok(a->G, a->hs, a->ws, a->hr, a->wr, a->Cp, a->Cr, a->Up)) return -2;
+  if (!a->plog || !a->b2 || !a->weight || !a->feat || !a->hid || !a->w2 || !a->wbar) return -3;
+  if (!a->tgt || !a->base || !a->map) return -3;
+  if (a->m < 1 || a->m > a->B) return -4;
+  if ((a->prec != 0 && a->prec != 1) || (a->logit != 0 && a->logit != 1) || (a->relu != 0 && a->relu != 1))
+    return -4;
+  if (a->prec)
+    hipLaunchKernelGGL(head_gradcam_kernel<1>, dim3((unsigned)a->m), dim3(256), 0, stream, *a);
+  else
+    hipLaunchKernelGGL(head_gradcam_kernel<0>, dim3((unsigned)a->m), dim3(256), 0, stream, *a);
+  return (int)hipGetLastError();
+}
+
 int gt_dense_dgrad(const DenseDgradArgs* a, hipStream_t stream) {
   if (a->Fp % 64 && a->Fp % 8) return -1;
   if (a->unpool_mask && (a->Cp % 8 || a->Hs % 2 || a->Ws % 2 || (long)(a->Hs / 2) * (a->Ws / 2) * a->Cp != a->Fp))
@@ -1347,6 +1560,8 @@ size_t gt_sizeof_head_predict_args() { return sizeof(HeadPredictArgs); }
 size_t gt_sizeof_head_ensemble_args() { return sizeof(HeadEnsembleArgs); }
 size_t gt_sizeof_head_tta_args() { return sizeof(HeadTtaArgs); }
 size_t gt_sizeof_head_occlusion_args() { return sizeof(HeadOcclusionArgs); }
+size_t gt_sizeof_cam_w1sum_args() { return sizeof(CamW1SumArgs); }
+size_t gt_sizeof_head_gradcam_args() { return sizeof(HeadGradcamArgs); }
 size_t gt_sizeof_dense_dgrad_args() { return sizeof(DenseDgradArgs); }
 size_t gt_sizeof_dense_wgrad_args() { return sizeof(DenseWgradAdamArgs); }
 

@@ -207,3 +207,10 @@ class GeneticCnnModel(GentunModel):
             raise RuntimeError("GeneticCnnModel.occlusion before fit()")
         kwargs.setdefault("device", self.device)
         return self.fitted.occlusion(x, **kwargs)
+
+    def gradcam(self, x, **kwargs):
+        """``self.fitted.gradcam`` on this model's device unless ``device`` says otherwise."""
+        if self.fitted is None:
+            raise RuntimeError("GeneticCnnModel.gradcam before fit()")
+        kwargs.setdefault("device", self.device)
+        return self.fitted.gradcam(x, **kwargs)

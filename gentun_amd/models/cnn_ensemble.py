@@ -24,8 +24,9 @@ import math
 import numpy as np
 import torch
 
-from .cnn_fitted import (CnnClassifier, TtaState, occlusion_by_views, occlusion_fill, occlusion_grid, occlusion_state,
-                         occlusion_targets, predict_batch, tta_views)
+from .cnn_fitted import (CnnClassifier, TtaState, cam_check, cam_check_hip, cam_upsample, gradcam_state,
+                         occlusion_by_views, occlusion_fill, occlusion_grid, occlusion_state, occlusion_targets,
+                         predict_batch, tta_views)
 
 FORMAT = "gentun-cnn-ensemble/1"
 OUTPUTS = ("proba", "label", "votes", "vote_label", "member_proba", "member_logits")
@@ -70,6 +71,16 @@ def combine(member_proba, weights):
     C = p.shape[2]
     votes = (np.argmax(p, axis=2)[:, :, None] == np.arange(C)[None, None, :]).sum(0).astype(np.int32)
     return acc.astype(np.float32), votes
+
+
+def combine_maps(member_maps, weights):
+    """The weighted mean of ``k`` equal-shape fp32 arrays in member order with :func:`combine`'s rounding
+    (``acc = w[0] * a[0]``, then ``acc = acc + w[g] * a[g]``)."""
+    w = np.asarray(weights, np.float32)
+    acc = w[0] * np.asarray(member_maps[0], np.float32)
+    for g in range(1, len(member_maps)):
+        acc = acc + w[g] * np.asarray(member_maps[g], np.float32)
+    return acc.astype(np.float32)
 
 
 def vote_label(votes, proba):
@@ -226,6 +237,41 @@ class CnnEnsemble(object):
             raise ValueError("unknown backend {!r}".format(backend))
         return (res[0], {"target": res[1], "base": res[2]}) if return_info else res[0]
 
+    def gradcam(self, x, target=None, score="logit", relu=True, upsample=False, device=None, batch=256,
+                backend=None, return_info=False):
+        """Grad-CAM of the ensemble (``CnnClassifier.gradcam``): fp32 ``[n, hr, wr]``, the weighted mean, in member
+        order, of the members' maps (``acc = w[0] * cam_0``, then ``acc = acc + w[g] * cam_g``, the product and
+        the sum rounded separately as in :func:`combine`). Every member's map is that of its own score (its logit
+        or its probability) of the ensemble's target, with its own ReLU applied first when ``relu=True``.
+        ``target=None``: the first maximum of the weighted mean of the members' probabilities.
+
+        With ``score="proba"`` and ``relu=False`` the mean is exactly the Grad-CAM of the combined probability
+        (the gradient is linear in the score). With ``relu=True`` the ReLU per member is a definition, not an
+        identity: a region that one member counts against the class does not cancel another member's support.
+        ``info["base"]`` is the weighted mean of the members' scores of the target: the combined probability, or
+        with ``score="logit"`` the weighted mean of the members' logits."""
+        cam_check(score, relu, upsample, batch)
+        x = self.members[0]._check_x(x)
+        target = occlusion_targets(target, x.shape[0], self.classes, "gradcam")
+        dev = torch.device("cpu" if device is None else device)
+        if backend is None:
+            backend = "hip" if dev.type == "cuda" else "torch"
+        if backend == "hip":
+            cam_check_hip(self.members[0].plan, self.input_shape)
+            res = self.hip_predictor(dev, batch).gradcam(x, target, score, bool(relu))
+        elif backend == "torch":
+            if target is None:
+                member = np.stack([m._torch_predict(x, dev, int(batch), torch.float32)[1] for m in self.members])
+                target = np.argmax(combine(member, self.weights)[0], axis=1).astype(np.int64)
+            per = [m._torch_gradcam(x, target, score, bool(relu), dev, int(batch), torch.float32)
+                   for m in self.members]
+            res = (combine_maps([p[0] for p in per], self.weights), target,
+                   combine_maps([p[2] for p in per], self.weights))
+        else:
+            raise ValueError("unknown backend {!r}".format(backend))
+        cam = cam_upsample(res[0], self.input_shape[:2]) if upsample else res[0]
+        return (cam, {"target": res[1], "base": res[2]}) if return_info else cam
+
     def hip_predictor(self, device, batch=256):
         """The cached :class:`HipEnsemblePredictor` of (device, rows per launch). The rows per launch are
         ``predict_batch(batch)`` lowered by the executor's rule for evaluation twins (``EVAL_TWIN_BUDGET``
@@ -297,6 +343,8 @@ class HipEnsemblePredictor(object):
                 self.heads[members] = a
         self._tta = {}               # views -> TtaState, created on first use
         self._occ = {}               # (patch, stride, fill, score) -> OcclusionState, created on first use
+        self._cam = {}               # (score, relu) -> GradcamState, created on first use
+        self._cam_wbar = None        # W1 summed over the real pixels (cam_wbar), on the first Grad-CAM request
 
     def _host(self, ens, EB):
         from . import cnn_engine as E
@@ -344,6 +392,11 @@ class HipEnsemblePredictor(object):
         """``(map, target, base)`` of validated arguments (``CnnEnsemble.occlusion``) over the ``k`` members and
         their weights."""
         return occlusion_state(self, patch, stride, fill, "proba", self.k, self.weight).run(self, x, target)
+
+    def gradcam(self, x, target, score, relu):
+        """``(map, target, base)`` of validated arguments (``CnnEnsemble.gradcam``) over the ``k`` members and
+        their weights."""
+        return gradcam_state(self, score, relu, self.k, self.weight).run(self, x, target)
 
     def run(self, x, members=False, views=None):
         """``x`` [n, H, W, C] host fp32 -> ``{"proba", "votes"}`` (+ ``"member_proba"``, ``"member_logits"``)

@@ -165,20 +165,84 @@ def occlusion_views(x, patch, stride=None, fill=0.0):
     return out
 
 
-def occlusion_targets(target, n, classes):
-    """``target`` of an occlusion request as ``None`` (the model's own label of every image) or int64 ``[n]``
-    from one class index or ``n`` of them in ``[0, classes)``."""
+def occlusion_targets(target, n, classes, what="occlusion"):
+    """``target`` of an occlusion (or Grad-CAM: ``what``) request as ``None`` (the model's own label of every
+    image) or int64 ``[n]`` from one class index or ``n`` of them in ``[0, classes)``."""
     if target is None:
         return None
     t = np.asarray(target)
     if t.dtype == np.bool_ or not np.issubdtype(t.dtype, np.integer) or t.ndim > 1:
-        raise ValueError("occlusion: target must be None, a class index or one class index per image")
+        raise ValueError("{}: target must be None, a class index or one class index per image".format(what))
     t = np.full(n, int(t), np.int64) if t.ndim == 0 else t.astype(np.int64)
     if t.shape != (n,):
-        raise ValueError("occlusion: {} targets for {} images".format(t.shape[0], n))
+        raise ValueError("{}: {} targets for {} images".format(what, t.shape[0], n))
     if n and (t.min() < 0 or t.max() >= classes):
-        raise ValueError("occlusion: targets must be in [0, {})".format(classes))
+        raise ValueError("{}: targets must be in [0, {})".format(what, classes))
     return t
+
+
+CAM_SCORES = ("logit", "proba")
+CAM_MAX_PIXELS = 1024        # CAM_MAXPX of csrc/hip/cnn_dense.hip
+
+
+def cam_shape(plan, input_shape):
+    """``(hr, wr)``, the real pixels of the last feature map of ``plan`` (the last stage's pooled map, what the
+    dense head flattens) for images of ``input_shape`` ``(H, W, C)``: every stage halves, rounding down --
+    8 x 8 for 32 x 32 with two stages, 7 x 7 for 28 x 28."""
+    stages = len(plan.kernels_per_layer)
+    hr, wr = int(input_shape[0]) >> stages, int(input_shape[1]) >> stages
+    if hr < 1 or wr < 1:
+        raise ValueError("{} stages leave no pixel of a {} x {} image".format(stages, input_shape[0], input_shape[1]))
+    return hr, wr
+
+
+def _bilinear_matrix(n_in, n_out):
+    """fp64 ``[n_out, n_in]``: bilinear interpolation with half-pixel centres, the source coordinate
+    ``(o + 0.5) * n_in / n_out - 0.5`` clamped at 0 and the right neighbour at ``n_in - 1``."""
+    src = np.maximum((np.arange(n_out) + 0.5) * (float(n_in) / float(n_out)) - 0.5, 0.0)
+    i0 = np.minimum(np.floor(src).astype(np.int64), n_in - 1)
+    i1 = np.minimum(i0 + 1, n_in - 1)
+    lam = src - i0
+    M = np.zeros((n_out, n_in), np.float64)
+    np.add.at(M, (np.arange(n_out), i0), 1.0 - lam)
+    np.add.at(M, (np.arange(n_out), i1), lam)
+    return M
+
+
+def cam_upsample(maps, size):
+    """``maps`` ``[n, hr, wr]`` -> fp32 ``[n, H, W]`` for ``size = (H, W)``: bilinear with half-pixel centres, the
+    rule of ``F.interpolate(mode="bilinear", align_corners=False)``, evaluated in fp64 and rounded once. Host
+    numpy only; the identity when the sizes match."""
+    maps = np.asarray(maps)
+    if maps.ndim != 3:
+        raise ValueError("cam_upsample: maps must be [n, hr, wr], got shape {}".format(maps.shape))
+    H, W = int(size[0]), int(size[1])
+    if H < 1 or W < 1:
+        raise ValueError("cam_upsample: size must be positive, got {!r}".format(size))
+    if (H, W) == maps.shape[1:]:
+        return maps.astype(np.float32)
+    My, Mx = _bilinear_matrix(maps.shape[1], H), _bilinear_matrix(maps.shape[2], W)
+    return np.einsum("yi,nij,xj->nyx", My, maps.astype(np.float64), Mx).astype(np.float32)
+
+
+def cam_check(score, relu, upsample, batch):
+    """The ``ValueError`` of a bad Grad-CAM option, before any work."""
+    if score not in CAM_SCORES:
+        raise ValueError("score {!r}: expected one of {}".format(score, CAM_SCORES))
+    for name, v in (("relu", relu), ("upsample", upsample)):
+        if not isinstance(v, (bool, np.bool_)):
+            raise ValueError("gradcam: {} must be a bool, got {!r}".format(name, v))
+    if not _is_int(batch) or int(batch) < 1:
+        raise ValueError("batch must be a positive integer")
+
+
+def cam_check_hip(plan, input_shape):
+    """The ``ValueError`` of a last feature map with more pixels than ``gt_head_gradcam`` takes, before a
+    predictor is built."""
+    hr, wr = cam_shape(plan, input_shape)
+    if hr * wr > CAM_MAX_PIXELS:
+        raise ValueError("gradcam: a last feature map of {} x {} pixels, at most {} on the HIP path".format(
+            hr, wr, CAM_MAX_PIXELS))
 
 
 def occlusion_by_views(scores, x, target, patch, stride, fill, batch, rows=4096):
@@ -404,6 +468,40 @@ class CnnClassifier(object):
             raise ValueError("unknown backend {!r}".format(backend))
         return (res[0], {"target": res[1], "base": res[2]}) if return_info else res[0]
 
+    def gradcam(self, x, target=None, score="logit", relu=True, upsample=False, device=None, batch=256,
+                backend=None, return_info=False):
+        """Grad-CAM (Selvaraju et al.) of ``x`` ``[n, H, W, C]`` (or one image) at the network's last feature map
+        ``A [C, hr, wr]`` (:func:`cam_shape`): fp32 ``[n, hr, wr]`` with
+        ``cam[i, j] = sum_c alpha[c] * A[c, i, j]``, ``alpha[c]`` the mean over the pixels of ``dS/dA[c]``, then
+        ``max(., 0)`` unless ``relu=False``. ``S`` is the logit (``score="logit"``) or the probability
+        (``"proba"``) of the target class: ``None`` for the model's own label (the first maximum of the
+        probabilities), one class index, or one per image. One forward per image; :meth:`occlusion` costs one per
+        grid cell.
+
+        ``upsample=True`` returns ``[n, H, W]`` by :func:`cam_upsample`, applied on the host after either
+        backend. ``return_info=True`` returns ``(map, {"target": int64 [n], "base": fp32 [n]})``, the classes
+        used and ``S(x[r])``.
+
+        ``device`` / ``backend`` / ``batch`` as in :meth:`predict`: the CPU or ``backend="torch"`` runs the
+        stock-torch forward up to ``A`` and the dense head under autograd; a ``cuda`` device runs the HIP
+        predictor's forward and ``gt_head_gradcam``, where the gradient collapses to the dense head's weights
+        (``gt_cam_w1sum``, once per predictor)."""
+        cam_check(score, relu, upsample, batch)
+        x = self._check_x(x)
+        target = occlusion_targets(target, x.shape[0], self.classes, "gradcam")
+        dev = torch.device("cpu" if device is None else device)
+        if backend is None:
+            backend = "hip" if dev.type == "cuda" else "torch"
+        if backend == "hip":
+            cam_check_hip(self.plan, self.input_shape)
+            res = self.hip_predictor(dev, batch).gradcam(x, target, score, bool(relu))
+        elif backend == "torch":
+            res = self._torch_gradcam(x, target, score, bool(relu), dev, int(batch), torch.float32)
+        else:
+            raise ValueError("unknown backend {!r}".format(backend))
+        cam = cam_upsample(res[0], self.input_shape[:2]) if upsample else res[0]
+        return (cam, {"target": res[1], "base": res[2]}) if return_info else cam
+
     def hip_predictor(self, device, batch=256):
         """The cached :class:`HipPredictor` of (device, rows per launch)."""
         dev = torch.device(device)
@@ -425,6 +523,10 @@ class CnnClassifier(object):
 
     def _torch_forward(self, xb, P):
         """``xb`` [n, C, H, W] -> logits [n, classes]: TorchFoldJob._forward(train=False), one group."""
+        return self._torch_head(self._torch_features(xb, P), P)
+
+    def _torch_features(self, xb, P):
+        """``xb`` [n, C, H, W] -> the output of the plan's last step [n, C_last, hr, wr]."""
         acts = {"input": xb}
         for st in self.plan.steps:
             if isinstance(st, ConvSpec):
@@ -440,9 +542,51 @@ class CnnClassifier(object):
                 acts[st.name] = F.relu(z)
             else:
                 acts[st.name] = F.max_pool2d(acts[st.srcs[0]], 2, 2)
-        feat = acts[self.plan.steps[-1].name].reshape(1, xb.shape[0], -1)
+        return acts[self.plan.steps[-1].name]
+
+    def _torch_head(self, A, P):
+        """The last feature map [n, C_last, hr, wr] -> logits [n, classes]."""
+        feat = A.reshape(1, A.shape[0], -1)
         h = F.relu(torch.baddbmm(P["dense1.b"][None, None, :], feat, P["dense1.w"][None]))
         return torch.baddbmm(P["dense2.b"][None, None, :], h, P["dense2.w"][None])[0]
+
+    def _torch_gradcam(self, x, target, score, relu, dev, batch, dtype):
+        """``(map [n, hr, wr], target int64 [n], base [n])`` by stock torch in ``dtype`` (fp32, or fp64: the
+        tests' oracle): the forward of :meth:`_torch_predict` up to the last feature map ``A`` without autograd,
+        then the dense head with autograd on ``A``, ``alpha = grad.mean((2, 3))``. Chunks of ``batch`` rows,
+        filled with zero images to a multiple of 32 exactly as :meth:`_torch_predict` fills them."""
+        P = self._tensors(dev, dtype)
+        n = x.shape[0]
+        h, w, c = self.input_shape
+        hr, wr = cam_shape(self.plan, self.input_shape)
+        ftype = np.float64 if dtype == torch.float64 else np.float32
+        cam, base, tgt = np.empty((n, hr, wr), ftype), np.empty(n, ftype), np.empty(n, np.int64)
+        for s in range(0, n, batch):
+            m = min(batch, n - s)
+            buf = np.zeros(((m + 31) // 32 * 32, c, h, w), np.float32)
+            buf[:m] = x[s:s + m].transpose(0, 3, 1, 2)
+            with torch.no_grad():
+                A = self._torch_features(torch.from_numpy(buf).to(device=dev, dtype=dtype), P)
+            A = A.detach().requires_grad_(True)
+            with torch.enable_grad():
+                logits = self._torch_head(A, P)
+                proba = torch.softmax(logits, dim=-1)
+                if target is None:                   # first maximum: the head kernels' scan
+                    t = np.argmax(proba[:m].detach().cpu().numpy(), axis=1).astype(np.int64)
+                else:
+                    t = target[s:s + m]
+                rows = torch.arange(m, device=dev)
+                picked = (logits if score == "logit" else proba)[rows, torch.from_numpy(t).to(dev)]
+                grad, = torch.autograd.grad(picked.sum(), A)
+            with torch.no_grad():
+                alpha = grad[:m].mean((2, 3))
+                cm = (alpha[:, :, None, None] * A[:m]).sum(1)
+                cam[s:s + m] = cm.cpu().numpy()
+                base[s:s + m] = picked.detach().cpu().numpy()
+            tgt[s:s + m] = t
+        if relu:
+            cam = np.maximum(cam, ftype(0))
+        return cam, tgt, base
 
     def _torch_predict(self, x, dev, batch, dtype):
         P = self._tensors(dev, dtype)
@@ -723,6 +867,91 @@ def occlusion_state(pred, patch, stride, fill, score, G, weight):
     return st
 
 
+def cam_wbar(pred, G):
+    """``wbar [G][Cp][Up]`` of a HIP predictor, ``W1`` summed over the real pixels of the last feature map
+    (``gt_cam_w1sum``): a constant of the loaded parameters, computed on the first Grad-CAM request."""
+    if pred._cam_wbar is None:
+        K, job = pred.K, pred.job
+        (hs, ws), (hr, wr) = job.final_hw, job.final_hw_real
+        wbar = torch.empty((G, job.final_cp, job.Up), dtype=torch.float32, device=pred.device)
+        a = K.CamW1SumArgs()
+        a.w1, a.wbar = job.views["W1"][0].data_ptr(), wbar.data_ptr()
+        a.G, a.hs, a.ws, a.hr, a.wr = G, hs, ws, hr, wr
+        a.Cp, a.Cr, a.Up = job.final_cp, job.members[0][0].kernels_per_layer[-1], job.Up
+        K.check(job.L.gt_cam_w1sum(a, job._stream()), "cam_w1sum")
+        pred._cam_wbar = wbar
+    return pred._cam_wbar
+
+
+class GradcamState(object):
+    """What a HIP predictor (``HipPredictor`` or ``HipEnsemblePredictor``) adds for one Grad-CAM setting
+    ``(score, relu)``: the arguments of ``gt_head_gradcam`` over the predictor's own buffers (the partial logits,
+    the pooled feature map and the hidden activations that ``gt_dense_fwd`` read and wrote, the fp32 masters of
+    ``W2`` and ``b2``, ``wbar``) and the results of one chunk. The predictor's job, evaluation launches, staging
+    tensor and ``upload`` are used as they are, at ``EB`` rows."""
+
+    def __init__(self, pred, score, relu, G, weight):
+        K, job, EB, dev = pred.K, pred.job, pred.EB, pred.device
+        (hs, ws), (hr, wr) = job.final_hw, job.final_hw_real     # at most CAM_MAX_PIXELS: cam_check_hip
+        self.hr, self.wr, self.weight = hr, wr, weight
+        self.wbar = cam_wbar(pred, G)
+        self.tgt = torch.empty(EB, dtype=torch.int32, device=dev)
+        self.base = torch.empty(EB, dtype=torch.float32, device=dev)
+        self.map = torch.empty((EB, hr, wr), dtype=torch.float32, device=dev)
+        a = K.HeadGradcamArgs()
+        a.plog, a.b2, a.weight = pred.df.plog, job.views["b2"][0].data_ptr(), weight.data_ptr()
+        a.feat, a.hid, a.w2, a.wbar = pred.df.x, pred.df.out, pred.df.w2, self.wbar.data_ptr()
+        a.tgt, a.base, a.map = self.tgt.data_ptr(), self.base.data_ptr(), self.map.data_ptr()
+        a.G, a.B, a.Up, a.C = G, EB, job.Up, pred.classes
+        a.hs, a.ws, a.hr, a.wr = hs, ws, hr, wr
+        a.Cp, a.Cr = job.final_cp, job.members[0][0].kernels_per_layer[-1]
+        a.prec, a.logit, a.relu = pred.df.prec, 1 if score == "logit" else 0, 1 if relu else 0
+        a.inv_n = float(np.float32(1) / np.float32(hr * wr))
+        self.head = a
+
+    def forward(self, pred, m):
+        """The launches of one chunk of ``m`` images on the current stream: staging tensor -> the predictor's
+        forward at ``EB`` rows -> ``map`` / ``tgt`` / ``base`` of the first ``m`` rows."""
+        job, K = pred.job, pred.K
+        s = job._stream()
+        self.head.m = m
+        job._run_fwd(s, pred.ops)
+        K.check(job.L.gt_dense_fwd(pred.df, s), "dense_fwd(gradcam)")
+        K.check(job.L.gt_head_gradcam(self.head, s), "head_gradcam")
+
+    def run(self, pred, x, target):
+        """``x`` [n, H, W, C] host fp32 -> ``(map [n, hr, wr], target int64 [n], base fp32 [n])`` as host arrays:
+        per chunk of ``EB`` images one upload and one launch set; the results gather on the device and are read
+        back once."""
+        n, EB, dev = x.shape[0], pred.EB, pred.device
+        with torch.cuda.device(dev):
+            out = torch.empty((n, self.hr, self.wr), dtype=torch.float32, device=dev)
+            tgt = torch.empty(n, dtype=torch.int32, device=dev)
+            base = torch.empty(n, dtype=torch.float32, device=dev)
+            for s in range(0, n, EB):
+                m = min(EB, n - s)
+                pred.upload(x[s:s + m])
+                if target is None:
+                    self.tgt.fill_(-1)               # the kernel puts the label there
+                else:
+                    self.tgt[:m].copy_(torch.from_numpy(target[s:s + m].astype(np.int32)).to(dev))
+                self.forward(pred, m)
+                out[s:s + m].copy_(self.map[:m])
+                tgt[s:s + m].copy_(self.tgt[:m])
+                base[s:s + m].copy_(self.base[:m])
+            return out.cpu().numpy(), tgt.cpu().numpy().astype(np.int64), base.cpu().numpy()
+
+
+def gradcam_state(pred, score, relu, G, weight):
+    """The cached :class:`GradcamState` of a predictor (its ``_cam`` dict) for one setting."""
+    key = (score, bool(relu))
+    st = pred._cam.get(key)
+    if st is None:
+        with torch.cuda.device(pred.device):
+            st = pred._cam[key] = GradcamState(pred, score, bool(relu), G, weight)
+    return st
+
+
 class HipPredictor(object):
     """Forward-only HIP launches of one fitted model at ``EB`` rows per launch.
 
@@ -772,6 +1001,8 @@ class HipPredictor(object):
         self._tta = {}               # views -> TtaState, created on first use
         self._occ = {}               # (patch, stride, fill, score) -> OcclusionState, created on first use
         self._one = None             # the one member's weight 1.0 on the device, for the occlusion head
+        self._cam = {}               # (score, relu) -> GradcamState, created on first use
+        self._cam_wbar = None        # W1 summed over the real pixels (cam_wbar), on the first Grad-CAM request
 
     def forward(self):
         """The launches of one chunk on the current stream: staging tensor -> ``logits`` / ``proba``."""
@@ -804,6 +1035,13 @@ class HipPredictor(object):
         if self._one is None:
             self._one = torch.ones(1, dtype=torch.float32, device=self.device)
         return occlusion_state(self, patch, stride, fill, score, 1, self._one).run(self, x, target)
+
+    def gradcam(self, x, target, score, relu):
+        """``(map, target, base)`` of validated arguments (``CnnClassifier.gradcam``): one member of weight 1.0
+        (``1.0f * v`` is ``v``)."""
+        if self._one is None:
+            self._one = torch.ones(1, dtype=torch.float32, device=self.device)
+        return gradcam_state(self, score, relu, 1, self._one).run(self, x, target)
 
     def run(self, x, views=None):
         """``x`` [n, H, W, C] host fp32 -> (logits, proba) host fp32 ``[n, classes]``; with ``views`` (a tuple

@@ -194,6 +194,22 @@ class HeadOcclusionArgs(C.Structure):
                 ("G", I), ("B", I), ("Up", I), ("C", I), ("m", I), ("Cc", I), ("w0", I), ("phase", I), ("logit", I)]
 
 
+class CamW1SumArgs(C.Structure):
+    """csrc/hip/cnn_dense.hip CamW1SumArgs: W1 summed over the real pixels of the last feature map, the constant
+    of a fitted model that Grad-CAM's channel weights need (gt_cam_w1sum)."""
+    _fields_ = [("w1", P), ("wbar", P), ("G", I), ("hs", I), ("ws", I), ("hr", I), ("wr", I), ("Cp", I), ("Cr", I),
+                ("Up", I)]
+
+
+class HeadGradcamArgs(C.Structure):
+    """csrc/hip/cnn_dense.hip HeadGradcamArgs: target, base score and Grad-CAM map of every image of a launch
+    (gt_head_gradcam)."""
+    _fields_ = [("plog", P), ("b2", P), ("weight", P), ("feat", P), ("hid", P), ("w2", P), ("wbar", P),
+                ("tgt", P), ("base", P), ("map", P), ("G", I), ("B", I), ("Up", I), ("C", I), ("m", I),
+                ("hs", I), ("ws", I), ("hr", I), ("wr", I), ("Cp", I), ("Cr", I), ("prec", I), ("logit", I),
+                ("relu", I), ("inv_n", C.c_float)]
+
+
 OCC_MAX_CELLS = 4096    # cells of one occlusion grid at most (csrc/hip/cnn_occlude.hip OCC_MAX_CELLS)
 
 
@@ -342,6 +358,14 @@ def lib():
         L.gt_head_occlusion.restype = I
         L.gt_sizeof_head_occlusion_args.restype = C.c_size_t
         assert L.gt_sizeof_head_occlusion_args() == C.sizeof(HeadOcclusionArgs), "HeadOcclusionArgs ABI mismatch"
+        L.gt_cam_w1sum.argtypes = [C.POINTER(CamW1SumArgs), P]
+        L.gt_cam_w1sum.restype = I
+        L.gt_sizeof_cam_w1sum_args.restype = C.c_size_t
+        assert L.gt_sizeof_cam_w1sum_args() == C.sizeof(CamW1SumArgs), "CamW1SumArgs ABI mismatch"
+        L.gt_head_gradcam.argtypes = [C.POINTER(HeadGradcamArgs), P]
+        L.gt_head_gradcam.restype = I
+        L.gt_sizeof_head_gradcam_args.restype = C.c_size_t
+        assert L.gt_sizeof_head_gradcam_args() == C.sizeof(HeadGradcamArgs), "HeadGradcamArgs ABI mismatch"
         L.gt_occlude_views.argtypes = [C.POINTER(OccludeArgs), P]
         L.gt_occlude_views.restype = I
         L.gt_sizeof_occlude_args.restype = C.c_size_t

@@ -20,6 +20,7 @@
 #   bash tools/gpu.sh cnn-augment             TrainConfig.augment: step time off / on (and the parent tree in ab_old/), gt_augment's kernel time (GROUPS_LIST= REPS= PROF_GROUPS= OUT=)
 #   bash tools/gpu.sh cnn-tta                 predict(tta=...): views and mean on the device vs V plain HIP predicts combined in numpy vs stock torch, classifier and k-ensemble (ROWS= FIT_ROWS= K= REPS= OUT=)
 #   bash tools/gpu.sh cnn-occlusion           occlusion(): copies built and packed on the device vs occlusion_views in numpy + plain HIP predicts vs stock torch, classifier and k-ensemble (ROWS= FIT_ROWS= K= REPS= OUT= TIME=)
+#   bash tools/gpu.sh cnn-gradcam             gradcam(): forward + gt_head_gradcam vs plain HIP predict (the floor) vs stock-torch autograd vs occlusion(patch=4), classifier and k-ensemble; the new kernels' device time by events and by a kernel trace run of its own (ROWS= OCC_ROWS= FIT_ROWS= K= REPS= OUT= TIME=)
 #   bash tools/gpu.sh rehearse                2-rank torchrun bench on one GPU (gloo control plane)
 #   bash tools/gpu.sh secondary               bench lines: reference fold semantics, torch comparator
 #
@@ -199,6 +200,20 @@ cnn-occlusion)
     --k ${K:-4} --reps ${REPS:-5} ${OCC_ARGS:-} > $out/bench.json 2> $out/bench.err; rc=$?
   [ $rc -eq 0 ] && tail -1 $out/bench.json | cut -c1-8000 || { tail -5 $out/bench.err; cut -c1-2000 $out/bench.json; }
   exit $rc ;;
+cnn-gradcam)
+  # the result line, then the new kernels' own durations from a kernel trace of one child run of its own (fits,
+  # then three gradcam calls per model); the files are kept under $OUT
+  out=${OUT:-/tmp/cnn_gradcam}; heartbeat; mkdir -p $out; rocprof_env; rm -rf /tmp/prof_cam
+  timeout -k 10 ${TIME:-900} python -u tools/bench_cnn_gradcam.py --rows ${ROWS:-10000} --occ-rows ${OCC_ROWS:-1000} \
+    --fit-rows ${FIT_ROWS:-2000} --k ${K:-4} --reps ${REPS:-5} ${CAM_ARGS:-} > $out/bench.json 2> $out/bench.err &&
+  tail -1 $out/bench.json | cut -c1-8000 &&
+  timeout -k 10 300 rocprofv3 --kernel-trace --stats -d /tmp/prof_cam -o run --output-format csv -- \
+    python3 tools/bench_cnn_gradcam.py --trace --rows ${ROWS:-10000} --fit-rows ${FIT_ROWS:-2000} --k ${K:-4} \
+    ${CAM_ARGS:-} > $out/prof.log 2>&1 &&
+  find /tmp/prof_cam -name "*kernel_stats.csv" -exec cp {} $out/kernel_stats.csv \; &&
+  grep -E "Name|gradcam|w1sum|head_predict|head_ensemble|dense_fwd" $out/kernel_stats.csv | cut -c1-300; rc=$?
+  [ $rc -eq 0 ] || { tail -5 $out/bench.err $out/prof.log 2>/dev/null; cut -c1-2000 $out/bench.json; }
+  exit $rc ;;
 rehearse)
   heartbeat
   GENTUN_DIST_BACKEND=gloo timeout -k 10 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node ${N:-2} \
@@ -220,5 +235,5 @@ secondary)
     cat gpurun_out/sec/torch.json
   fi ;;
 *)
-  sed -n 2,24p "$0"; exit 2 ;;
+  sed -n 2,25p "$0"; exit 2 ;;
 esac
