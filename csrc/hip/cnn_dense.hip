@@ -23,6 +23,7 @@
 
 #include <algorithm>
 #include <cstdlib>
+#include <cstring>
 
 #include "common.h"
 
@@ -422,6 +423,88 @@ __global__ void __launch_bounds__(64) head_fwd_kernel(HeadArgs a) {
     float dp[HEAD_MAXC], s = 0.f;
     for (int c = 0; c < C; ++c) {
       const float yc = (c == y) ? 1.f : 0.f;
+      const bool inside = p[c] >= CLIP_EPS && p[c] <= 1.f - CLIP_EPS;
+      const float pc = fminf(fmaxf(p[c], CLIP_EPS), 1.f - CLIP_EPS);
+      dp[c] = inside ? (pc - yc) / (pc * (1.f - pc)) / C : 0.f;
+      s += p[c] * dp[c];
+    }
+    for (int c = 0; c < C; ++c) dz[c] = p[c] * (dp[c] - s) * inv_b;
+  }
+}
+
+// Soft-target training head (label smoothing, distillation; models/cnn_engine.py "The target row"): HeadArgs
+// plus the target of every training row -- row `sid` of a table of probabilities, or the two values of a
+// smoothed label. Training only.
+struct HeadSoftArgs {
+  HeadArgs h;
+  const float* soft;       // [N][C] fp32 target rows indexed by sample id, or null: label smoothing
+  float t_on, t_off;       // soft == null: the target of the labelled class / of every other class
+};
+
+// head_fwd_kernel's training path with `yc` read from the target row. The partial-logit reduction and the
+// softmax repeat head_fwd_kernel's code operation for operation, and yc stands exactly where
+// (c == y) ? 1.f : 0.f stands there: a table of exact one-hot rows (or t_on = 1, t_off = 0) writes the dz
+// gt_head writes, bit for bit.
+__global__ void __launch_bounds__(64) head_fwd_soft_kernel(HeadSoftArgs sa) {
+  const HeadArgs& a = sa.h;
+  const int idx = blockIdx.x, lane = threadIdx.x;
+  const int g = idx / a.B, b = idx % a.B;
+  const int C = a.C, nt = a.Up / 16;
+  // the target chain (step -> sample id -> label / table row: dependent loads) issued first, so it runs
+  // beside the partial-logit loads instead of after the reduction; every class of the row at once
+  // (clamped index), as the partial logits are loaded
+  const int step = a.st ? a.st->cur_step : 0;
+  const long sid = a.gather[((long)step * a.G + g) * a.B + b];
+  float tv[HEAD_MAXC];
+  if (sa.soft) {
+    const float* tr = sa.soft + sid * C;
+#pragma unroll
+    for (int c = 0; c < HEAD_MAXC; ++c) tv[c] = tr[min(c, C - 1)];
+  } else {
+    const int y = (int)a.labels[sid];
+#pragma unroll
+    for (int c = 0; c < HEAD_MAXC; ++c) tv[c] = (c == y) ? sa.t_on : sa.t_off;
+  }
+  float acc[HEAD_MAXC];
+  const float* pl = a.plog + ((long)g * nt * a.B + b) * C;
+#pragma unroll
+  for (int c = 0; c < HEAD_MAXC; ++c) acc[c] = 0.f;
+  for (int t = lane; t < nt; t += 64) {
+    float v[HEAD_MAXC];
+#pragma unroll
+    for (int c = 0; c < HEAD_MAXC; ++c) v[c] = pl[(long)t * a.B * C + min(c, C - 1)];
+#pragma unroll
+    for (int c = 0; c < HEAD_MAXC; ++c) acc[c] += c < C ? v[c] : 0.f;
+  }
+#pragma unroll
+  for (int c = 0; c < HEAD_MAXC; ++c) {
+    if (c < C) {
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) acc[c] += __shfl_xor(acc[c], o);
+    }
+  }
+  if (lane != 0) return;
+  float logit[HEAD_MAXC];
+  for (int c = 0; c < C; ++c) logit[c] = acc[c] + a.b2[(long)g * C + c];
+  float p[HEAD_MAXC];
+  float mx = -INFINITY;
+  for (int c = 0; c < C; ++c) mx = fmaxf(mx, logit[c]);
+  float z = 0.f;
+  for (int c = 0; c < C; ++c) { p[c] = expf(logit[c] - mx); z += p[c]; }
+  for (int c = 0; c < C; ++c) p[c] /= z;
+  float* dz = a.dz + ((long)g * a.B + b) * C;
+  // mean over the batch's real rows; padding rows of a short batch: zero weight
+  const int nv = a.valid ? a.valid[(long)step * a.G + g] : a.B;
+  const int nn = a.valid_norm ? a.valid_norm[(long)step * a.G + g] : nv;
+  const float inv_b = (b < nv && nn > 0) ? 1.0f / nn : 0.f;
+  if (a.loss_ce) {
+    // exact for any target row that sums to 1
+    for (int c = 0; c < C; ++c) dz[c] = (p[c] - tv[c]) * inv_b;
+  } else {
+    // dL/dp_c = (pc - t_c)/(pc(1-pc)) / C inside the clip range, 0 where clipped
+    float dp[HEAD_MAXC], s = 0.f;
+    for (int c = 0; c < C; ++c) {
+      const float yc = tv[c];
       const bool inside = p[c] >= CLIP_EPS && p[c] <= 1.f - CLIP_EPS;
       const float pc = fminf(fmaxf(p[c], CLIP_EPS), 1.f - CLIP_EPS);
       dp[c] = inside ? (pc - yc) / (pc * (1.f - pc)) / C : 0.f;
@@ -1433,6 +1516,29 @@ int gt_head(const HeadArgs* a, hipStream_t stream) {
   return (int)hipGetLastError();
 }
 
+// finite: the exponent bits are not all ones (read off the bits, whatever the floating-point flags of the build)
+static inline bool finite_bits(float v) {
+  uint32_t u;
+  memcpy(&u, &v, sizeof(u));
+  return (u & 0x7f800000u) != 0x7f800000u;
+}
+
+// The training head on soft targets: head_fwd_soft_kernel, then the unchanged head_bwd_kernel on the embedded
+// HeadArgs. Refuses (negative code, nothing launched) what the kernels cannot run.
+int gt_head_soft(const HeadSoftArgs* sa, hipStream_t stream) {
+  if (!sa) return -4;
+  const HeadArgs* a = &sa->h;
+  if (a->eval) return -1;                                               // training only
+  if (a->G < 1 || a->B < 1 || a->B > HEAD_MAXB || a->C < 1 || a->C > HEAD_MAXC) return -1;
+  if (a->Up < 16 || a->Up % 16) return -2;
+  if (!a->plog || !a->b2 || !a->labels || !a->gather || !a->dz) return -3;
+  if (!a->h || !a->w2 || !a->dH || !a->gw2 || !a->gb2 || !a->gb1) return -3;     // head_bwd_kernel's operands
+  if (!sa->soft && !(finite_bits(sa->t_on) && finite_bits(sa->t_off))) return -5;
+  hipLaunchKernelGGL(head_fwd_soft_kernel, dim3(a->G * a->B), dim3(64), 0, stream, *sa);
+  hipLaunchKernelGGL(head_bwd_kernel, dim3((a->Up + 63) / 64, a->G), dim3(256), 0, stream, *a);
+  return (int)hipGetLastError();
+}
+
 int gt_head_predict(const HeadPredictArgs* a, hipStream_t stream) {
   if (a->C < 1 || a->C > HEAD_MAXC || a->G < 1 || a->B < 1) return -1;
   if (a->Up < 16 || a->Up % 16) return -2;
@@ -1556,6 +1662,7 @@ size_t gt_sizeof_adam_seg() { return sizeof(AdamSeg); }
 int gt_adam_block_elems() { return ADAM_BLK; }
 size_t gt_sizeof_dense_fwd_args() { return sizeof(DenseFwdArgs); }
 size_t gt_sizeof_head_args() { return sizeof(HeadArgs); }
+size_t gt_sizeof_head_soft_args() { return sizeof(HeadSoftArgs); }
 size_t gt_sizeof_head_predict_args() { return sizeof(HeadPredictArgs); }
 size_t gt_sizeof_head_ensemble_args() { return sizeof(HeadEnsembleArgs); }
 size_t gt_sizeof_head_tta_args() { return sizeof(HeadTtaArgs); }

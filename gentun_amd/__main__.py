@@ -186,6 +186,14 @@ def augment_setting(args):
     return {"shift": shift, "flip": flip} if (shift or flip) else None
 
 
+def label_smoothing_setting(args):
+    """``TrainConfig.label_smoothing`` of ``--label-smoothing EPS`` (0.0 when it is not given)."""
+    eps = float(getattr(args, "label_smoothing", 0.0) or 0.0)
+    if not (0.0 <= eps < 1.0):
+        raise SystemExit("--label-smoothing must be in [0, 1)")
+    return eps
+
+
 def cmd_cnn(args):
     from . import GeneticCnnIndividual
     from .utils.data import make_glyph_classification, make_variant_classification
@@ -204,14 +212,19 @@ def cmd_cnn(args):
                  epochs=_ints(args.epochs), learning_rate=_floats(args.lr), batch_size=args.batch, loss=args.loss,
                  seed=args.seed, optimizer=args.optimizer, momentum=args.momentum, dtype=args.dtype,
                  reset=args.fold_reset, batching=args.batching, batch_norm=args.batch_norm,
-                 augment=augment_setting(args))
+                 augment=augment_setting(args), label_smoothing=label_smoothing_setting(args))
     keep = {}
     out = _run_search(args, GeneticCnnIndividual, x, y, extra, maximize=True, keep=keep)
     if out is not None and args.save_model:
         print(json.dumps(save_cnn_model(args.save_model, x, y, out["best_genes"], extra, device=_device())))
+    if getattr(args, "distill", None) and not args.save_ensemble:
+        raise SystemExit("--distill needs --save-ensemble (the teacher)")
     if out is not None and args.save_ensemble:
         print(json.dumps(save_cnn_ensemble(args.save_ensemble, x, y, keep["population"], args.ensemble_size, extra,
-                                           device=_device())))
+                                           device=_device(), keep=keep)))
+        if getattr(args, "distill", None):
+            print(json.dumps(save_cnn_student(args.distill, x, y, keep["ensemble"], extra, args.distill_alpha,
+                                              args.distill_temperature, device=_device())))
     return out
 
 
@@ -225,7 +238,17 @@ def save_cnn_model(path, x, y, genes, extra, device=None):
     return {"saved_model": path, "genes": clf.genes, "metrics": clf.metrics}
 
 
-def save_cnn_ensemble(path, x, y, population, size, extra, device=None):
+def save_cnn_student(path, x, y, ensemble, extra, alpha, temperature, device=None):
+    """``--distill`` of the ``cnn`` sub-command (rank 0): fit a student with the first member's genes on all rows
+    against a blend of the hard labels and the ensemble's probabilities, with the search's own settings, and
+    write the classifier (.npz). Returns the line that is printed."""
+    clf = ensemble.distill(x, y, alpha=alpha, temperature=temperature, device=device, **extra)
+    clf.save(path)
+    return {"saved_student": path, "genes": clf.genes, "metrics": clf.metrics, "alpha": alpha,
+            "temperature": temperature}
+
+
+def save_cnn_ensemble(path, x, y, population, size, extra, device=None, keep=None):
     """``--save-ensemble`` of the ``cnn`` sub-command (rank 0): refit the ``size`` fittest distinct genomes of
     the last evaluated generation on all rows with the search's own settings, as one ensemble, and write it
     (.npz). Returns the line that is printed."""
@@ -235,6 +258,8 @@ def save_cnn_ensemble(path, x, y, population, size, extra, device=None):
         raise SystemExit("--save-ensemble: the final population holds no evaluated individual")
     ens = fit_ensemble(x, y, genomes, device=device, **extra)
     ens.save(path)
+    if keep is not None:
+        keep["ensemble"] = ens
     return {"saved_ensemble": path, "genes": [m.genes for m in ens.members], "metrics": ens.metrics,
             "member_metrics": [m.metrics for m in ens.members]}
 
@@ -325,6 +350,9 @@ def main(argv=None):
                    help="training-time augmentation: random translation by up to N pixels with zero fill (0: off)")
     c.add_argument("--augment-flip", action="store_true",
                    help="training-time augmentation: random horizontal flip (off by default)")
+    c.add_argument("--label-smoothing", type=float, default=0.0, metavar="EPS",
+                   help="train on smoothed labels: 1 - EPS + EPS / classes for the labelled class, EPS / classes "
+                        "for the others (0: off)")
     c.add_argument("--save-model", default=None, metavar="PATH",
                    help="after the search, refit the fittest individual on all rows and write the classifier (.npz)")
     c.add_argument("--save-ensemble", default=None, metavar="PATH",
@@ -332,6 +360,13 @@ def main(argv=None):
                         "rows and write them as one ensemble (.npz)")
     c.add_argument("--ensemble-size", type=int, default=3, metavar="K",
                    help="members of --save-ensemble (1 to 64; fewer when fewer distinct genomes were evaluated)")
+    c.add_argument("--distill", default=None, metavar="PATH",
+                   help="with --save-ensemble: distill the ensemble into one student with the first member's genes, "
+                        "trained on all rows, and write the classifier (.npz)")
+    c.add_argument("--distill-alpha", type=float, default=0.5, metavar="A",
+                   help="--distill: weight of the teacher's probabilities in the targets (0: hard labels only)")
+    c.add_argument("--distill-temperature", type=float, default=1.0, metavar="T",
+                   help="--distill: temperature of the teacher's softmax")
     c.set_defaults(fn=cmd_cnn)
     x = sub.add_parser("xgb", help="GBDT (XGBoost-style) hyper-parameter search")
     _common(x)

@@ -278,7 +278,9 @@ class GeneticCnnIndividual(Individual):
     reference's "KFold i/n" / "Training N epochs with learning rate lr" lines,
     keras_models.py:134,137) and ``augment`` (None = the reference's training on the raw
     images; ``{"shift": s, "flip": bool}`` = the Genetic-CNN paper's random translation
-    with zero fill and random horizontal flip, re-drawn every step on the device).
+    with zero fill and random horizontal flip, re-drawn every step on the device) and
+    ``label_smoothing`` (0.0 = hard labels; ``eps`` in (0, 1) = the training targets
+    ``1 - eps + eps / classes`` for the labelled class and ``eps / classes`` for the others).
     """
 
     def __init__(self, x_train, y_train, genome=None, genes=None, crossover_rate=0.3, mutation_rate=0.1,
@@ -287,7 +289,7 @@ class GeneticCnnIndividual(Individual):
                  nfold=5, epochs=(3,), learning_rate=(1e-3,), batch_size=32,
                  loss='bce_compat', dtype='fp32', seed=0, backend=None, device=None, optimizer='adam',
                  momentum=0.9, reset='kernels', batching='keras', batch_norm=False, verbose=False,
-                 pad_images=True, augment=None):
+                 pad_images=True, augment=None, label_smoothing=0.0):
         if genome is None:
             genome = {'S_{}'.format(i + 1): k * (k - 1) // 2 for i, k in enumerate(nodes)}
         if genes is None:
@@ -324,6 +326,8 @@ class GeneticCnnIndividual(Individual):
         self.pad_images = bool(pad_images)
         # training-time augmentation: None or {"shift": s, "flip": bool} (TrainConfig.augment)
         self.augment = None if augment is None else dict(augment)
+        # label smoothing of the training targets (TrainConfig.label_smoothing; 0.0: off)
+        self.label_smoothing = label_smoothing
 
     @staticmethod
     def generate_random_genes(genome):
@@ -342,7 +346,8 @@ class GeneticCnnIndividual(Individual):
                                seed=self.seed, backend=self.backend, device=device or self.device,
                                optimizer=self.optimizer, momentum=self.momentum, reset=self.reset,
                                batching=self.batching, batch_norm=self.batch_norm,
-                               verbose=self.verbose, pad_images=self.pad_images, augment=self.augment)
+                               verbose=self.verbose, pad_images=self.pad_images, augment=self.augment,
+                               label_smoothing=self.label_smoothing)
 
     def cost(self):
         """Relative training cost (forward FLOPs/sample); LPT scheduling key."""
@@ -382,6 +387,7 @@ class GeneticCnnIndividual(Individual):
             'verbose': self.verbose,
             'pad_images': self.pad_images,
             'augment': self.augment,
+            'label_smoothing': self.label_smoothing,
         }
 
     def mutate(self):

@@ -2,3 +2,4 @@
 
 from .generic_models import GentunModel  # noqa: F401
 from .cnn_ensemble import CnnEnsemble, fit_ensemble  # noqa: F401
+from .cnn_distill import distill, soft_targets  # noqa: F401

@@ -29,7 +29,7 @@ class GeneticCnnModel(GentunModel):
                  dropout_probability, classes, nfold=5, epochs=(3,), learning_rate=(1e-3,), batch_size=32,
                  loss="bce_compat", dtype="fp32", seed=0, backend=None, device=None, fold_parallel=True,
                  optimizer="adam", momentum=0.9, reset="kernels", batching="keras", batch_norm=False,
-                 verbose=False, pad_images=True, augment=None):
+                 verbose=False, pad_images=True, augment=None, label_smoothing=0.0):
         super(GeneticCnnModel, self).__init__(x_train, y_train)
         self.genes = dict(genes)
         self.name = '-'.join(self.genes[k] for k in sorted(self.genes))
@@ -60,7 +60,8 @@ class GeneticCnnModel(GentunModel):
                                     dropout=dropout_probability, loss=loss, dtype=dtype, seed=seed,
                                     optimizer=optimizer, momentum=momentum, reset=reset, batching=batching,
                                     batch_norm=batch_norm, verbose=verbose, nfold=nfold, pad_images=pad_images,
-                                    augment=_eng.normalize_augment(augment, hw=self.input_shape[:2]))
+                                    augment=_eng.normalize_augment(augment, hw=self.input_shape[:2]),
+                                    label_smoothing=label_smoothing)
         self.fold_parallel = fold_parallel
         self.model = self.build_model(self.genes, self.nodes, self.input_shape, self.kernels_per_layer,
                                       self.kernel_sizes, self.dense_units, self.dropout_probability, self.classes)
@@ -172,9 +173,14 @@ class GeneticCnnModel(GentunModel):
         return self.collect(results)
 
     # ------------------------------------------------------------ the final model
-    def fit(self):
+    def fit(self, soft_targets=None):
         """Train this candidate on every row of ``x_train`` with the model's own ``TrainConfig`` and keep
         the result as ``self.fitted``, a :class:`~gentun_amd.models.cnn_fitted.CnnClassifier`.
+
+        ``soft_targets``: an fp32 ``[len(x_train), classes]`` table of target rows (non-negative, every row
+        summing to 1) the training step learns from instead of the hard labels, e.g. a teacher's
+        probabilities (:mod:`~gentun_amd.models.cnn_distill`). The metrics below are still those against
+        the hard labels ``argmax(y_train)``.
 
         One group in one job whose fold is (all rows, all rows): the job's evaluation then reports the
         training-set metrics in evaluation mode (``fitted.metrics``). The fold id is ``nfold``, one past
@@ -185,7 +191,7 @@ class GeneticCnnModel(GentunModel):
         from .cnn_fitted import CnnClassifier
         rows = np.arange(len(self.x_train))
         job = _eng.make_job(self.backend, self.model, self.x_train, self.y_train, [(rows, rows)], self.cfg,
-                            self.device, fold_ids=[self.nfold])
+                            self.device, fold_ids=[self.nfold], soft_targets=soft_targets)
         job.launch()
         res = job.finish()
         self.jobs = [job]

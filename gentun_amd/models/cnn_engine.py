@@ -116,6 +116,78 @@ def normalize_augment(augment, hw=None):
     return {"shift": int(shift), "flip": bool(flip)}
 
 
+# ---------------------------------------------------------------------------
+# Soft targets of the training step (label smoothing, distillation)
+#
+# The target row. For a training row with sample id ``sid`` and hard label ``y`` the target is t[0..C):
+#   neither setting      t[c] = [c == y]                         (the hard-label path, untouched)
+#   label_smoothing=eps  t[c] = t_on if c == y else t_off        (smoothing_targets(eps, C))
+#   a table T [N, C]     t[c] = T[sid, c]
+# The losses are the hard-label expressions with the one-hot entry replaced by t[c]:
+#   ce          loss = -sum_c t[c] log(max(p[c], 1e-30));  dz[c] = (p[c] - t[c]) * inv_b  (exact: sum t = 1)
+#   bce_compat  dp[c] = inside ? (pc - t[c]) / (pc (1 - pc)) / C : 0;  dz[c] = p[c] (dp[c] - s) * inv_b,
+#               s = sum_c p[c] dp[c]
+# inv_b and the real-row counts of a short batch are unchanged. Evaluation (CV scoring, fit's metrics,
+# predict) stays on the hard labels argmax(y).
+# ---------------------------------------------------------------------------
+
+SOFT_ROW_SUM_TOL = 1e-4     # a table row must sum to 1 within this
+
+
+def normalize_label_smoothing(eps):
+    """``label_smoothing`` as a float in ``[0, 1)``; 0.0 is "off". ``ValueError`` on anything else
+    (``bool`` included)."""
+    if eps is None:
+        return 0.0
+    if isinstance(eps, (bool, np.bool_)) or not isinstance(eps, (int, float, np.integer, np.floating)):
+        raise ValueError("label_smoothing must be a real number in [0, 1)")
+    eps = float(eps)
+    if not (0.0 <= eps < 1.0):                   # NaN fails both comparisons
+        raise ValueError("label_smoothing must be in [0, 1), got {}".format(eps))
+    return eps
+
+
+def smoothing_targets(eps, classes):
+    """``(t_on, t_off)`` of label smoothing as numpy fp32 scalars: ``t_off = fp32(eps) / fp32(C)`` and
+    ``t_on = (fp32(1) - fp32(eps)) + t_off``, every operation rounded to fp32. Both executors call this."""
+    e, c = np.float32(eps), np.float32(classes)
+    t_off = np.float32(e / c)
+    t_on = np.float32(np.float32(np.float32(1.0) - e) + t_off)
+    return t_on, t_off
+
+
+def check_soft_targets(table, n, classes):
+    """A soft-target table as contiguous fp32 ``[n, classes]``: finite, every entry >= 0, every row sum
+    within ``SOFT_ROW_SUM_TOL`` of 1. ``ValueError`` otherwise."""
+    try:
+        t = np.asarray(table)
+    except Exception:
+        raise ValueError("soft_targets must be an array of shape [{}, {}]".format(n, classes))
+    if t.dtype == object or t.dtype.kind not in "fiu":
+        raise ValueError("soft_targets must be a real-valued array")
+    if t.shape != (int(n), int(classes)):
+        raise ValueError("soft_targets must have shape [{}, {}] (one row per training row), got {}".format(
+            n, classes, list(t.shape)))
+    if not np.isfinite(t).all():
+        raise ValueError("soft_targets must be finite")
+    if (t < 0).any():
+        raise ValueError("soft_targets must not be negative")
+    if (np.abs(t.astype(np.float64).sum(1) - 1.0) > SOFT_ROW_SUM_TOL).any():
+        raise ValueError("soft_targets: every row must sum to 1 within {}".format(SOFT_ROW_SUM_TOL))
+    return np.ascontiguousarray(t, dtype=np.float32)
+
+
+def check_soft_settings(cfg, soft_targets, n, classes):
+    """The checks of a job's soft-target settings, before any work: the table (returned as contiguous
+    fp32, or None) and that it does not come together with ``cfg.label_smoothing``."""
+    eps = normalize_label_smoothing(getattr(cfg, "label_smoothing", 0.0))
+    if soft_targets is None:
+        return None
+    if eps > 0.0:
+        raise ValueError("soft_targets and label_smoothing are both given; smooth the table's rows instead")
+    return check_soft_targets(soft_targets, n, classes)
+
+
 def augment_images(x, dy, dx, flip, hw_real):
     """The augmentation of a stack of images ``x [..., H, W]`` (any leading dimensions; H x W may be a
     zero-padded extent around the real ``hw_real``) under per-image draws ``dy, dx, flip`` (integer tensors
@@ -141,7 +213,7 @@ class TrainConfig(object):
     def __init__(self, epochs=(3,), learning_rate=(1e-3,), batch_size=32, dropout=0.5, loss="bce_compat",
                  dtype="fp32", seed=0, use_graph=None, eval_batch=1000, optimizer="adam", momentum=0.9,
                  reset="kernels", batching="keras", batch_norm=False, bn_momentum=0.99, bn_eps=1e-3,
-                 dp_group=None, verbose=False, nfold=None, pad_images=True, augment=None):
+                 dp_group=None, verbose=False, nfold=None, pad_images=True, augment=None, label_smoothing=0.0):
         if isinstance(epochs, int):
             epochs = (epochs,)
         if isinstance(learning_rate, (int, float)):
@@ -192,6 +264,9 @@ class TrainConfig(object):
         # optional training-time augmentation (off by default): a random translation by up to ``shift``
         # pixels with zero fill and a random horizontal flip, drawn per step and batch row on the device
         self.augment = normalize_augment(augment)
+        # optional label smoothing of the training targets (0.0: off, the hard labels); evaluation always
+        # scores against the hard labels
+        self.label_smoothing = normalize_label_smoothing(label_smoothing)
 
     def total_epochs(self):
         return sum(self.epochs)
@@ -267,7 +342,12 @@ class FoldJob(object):
 
     layout = "nchw"
 
-    def __init__(self, plan, x, y, folds, cfg, device, fold_ids=None, stream=None, members=None):
+    def __init__(self, plan, x, y, folds, cfg, device, fold_ids=None, stream=None, members=None,
+                 soft_targets=None):
+        # soft targets (see "The target row" above): checked before any work
+        p0 = plan if plan is not None else (members[0][0] if members else None)
+        self.soft_np = check_soft_settings(cfg, soft_targets, len(x), p0.classes) if p0 is not None else None
+        self.smooth = normalize_label_smoothing(getattr(cfg, "label_smoothing", 0.0))
         self.multi = members is not None
         if members is None:
             members = [(plan, folds, list(range(len(folds))) if fold_ids is None else list(fold_ids))]
@@ -302,6 +382,9 @@ class FoldJob(object):
         # with the fold id, the global step and the full-batch row they fix every draw (utils/rng.aug_draws)
         self.aug = normalize_augment(getattr(cfg, "augment", None), hw=self.plan.input_shape[:2])
         self.aug_seeds = [_rng.stable_hash(self.member_seeds[c], "dropout") & 0xFFFFFFFF for c in self.gmember]
+        # the target table: one device tensor per job, shared by all groups (None: hard labels or smoothing)
+        self.soft = None if self.soft_np is None else torch.from_numpy(self.soft_np).to(self.device)
+        self.smooth_on_off = smoothing_targets(self.smooth, self.data.classes) if self.smooth > 0.0 else None
         # device index tables
         maxn = max(ntr)
         tm = np.zeros((self.G, maxn), np.int64)
@@ -911,6 +994,20 @@ class TorchFoldJob(FoldJob):
         self._dp_rows = (r0, r1)
         return grp, rank, world, r0, r1
 
+    def _train_targets(self):
+        """The ``[N, C]`` target rows of the training step: the hard labels' one-hot rows, the job's table, or
+        the smoothed labels. Evaluation keeps ``self.data.onehot``."""
+        if self.soft is not None:
+            return self.soft
+        if self.smooth_on_off is not None:
+            t = getattr(self, "_smooth_rows", None)
+            if t is None:
+                t_on, t_off = (float(v) for v in self.smooth_on_off)
+                oh = self.data.onehot
+                t = self._smooth_rows = torch.where(oh > 0, torch.full_like(oh, t_on), torch.full_like(oh, t_off))
+            return t
+        return self.data.onehot
+
     def train_step(self):
         dp = self._dp()
         idx = self.epoch_idx.index_select(0, self.step_ctr).view(self.G, self.B)
@@ -924,7 +1021,7 @@ class TorchFoldJob(FoldJob):
         xb = self._gather(idx)
         if self.aug is not None:
             xb = self._augment(xb, dp[3] if dp is not None else 0)
-        yb = self.data.onehot.index_select(0, idx.reshape(-1)).view(self.G, idx.shape[1], -1)
+        yb = self._train_targets().index_select(0, idx.reshape(-1)).view(self.G, idx.shape[1], -1)
         self.flat.grad.zero_()
         if self.amp:
             with torch.autocast(device_type="cuda", dtype=torch.bfloat16):
@@ -1084,23 +1181,26 @@ class TorchPopJob(TorchFoldJob):
         return self._head(feat, train, P)
 
 
-def _one_job(backend, plan, x, y, folds, cfg, device, fold_ids, stream):
+def _one_job(backend, plan, x, y, folds, cfg, device, fold_ids, stream, soft_targets=None):
+    extra = {} if soft_targets is None else {"soft_targets": soft_targets}
     if backend == "torch":
-        return TorchFoldJob(plan, x, y, folds, cfg, device, fold_ids=fold_ids, stream=stream)
+        return TorchFoldJob(plan, x, y, folds, cfg, device, fold_ids=fold_ids, stream=stream, **extra)
     if backend == "hip":
         from .cnn_hip import HipPopJob
-        return HipPopJob(plan, x, y, folds, cfg, device, fold_ids=fold_ids, stream=stream)
+        return HipPopJob(plan, x, y, folds, cfg, device, fold_ids=fold_ids, stream=stream, **extra)
     raise ValueError("unknown backend {!r}".format(backend))
 
 
-def make_job(backend, plan, x, y, folds, cfg, device, fold_ids=None, stream=None):
+def make_job(backend, plan, x, y, folds, cfg, device, fold_ids=None, stream=None, soft_targets=None):
     """Job training ``folds`` of one architecture: concurrent folds
     (``cfg.reset == "all"``) or the reference's sequential folds with
-    carried-over biases (``"kernels"``)."""
+    carried-over biases (``"kernels"``). ``soft_targets``: an fp32 ``[len(x), classes]`` table of target
+    rows the training step learns from instead of the hard labels (checked here, before a job is built)."""
     ids = list(range(len(folds))) if fold_ids is None else list(fold_ids)
+    soft = check_soft_settings(cfg, soft_targets, len(x), plan.classes)
     if cfg.reset == "all" or len(folds) == 1:
-        return _one_job(backend, plan, x, y, folds, cfg, device, ids, stream)
-    return SequentialFoldJob(lambda f: _one_job(backend, plan, x, y, [folds[f]], cfg, device, [ids[f]], stream),
+        return _one_job(backend, plan, x, y, folds, cfg, device, ids, stream, soft)
+    return SequentialFoldJob(lambda f: _one_job(backend, plan, x, y, [folds[f]], cfg, device, [ids[f]], stream, soft),
                              len(folds), multi=False, spec=lambda f: ([folds[f]], [ids[f]]))
 
 

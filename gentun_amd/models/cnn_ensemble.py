@@ -272,6 +272,13 @@ class CnnEnsemble(object):
         cam = cam_upsample(res[0], self.input_shape[:2]) if upsample else res[0]
         return (cam, {"target": res[1], "base": res[2]}) if return_info else cam
 
+    def distill(self, x, y_onehot, genes=None, alpha=0.5, temperature=1.0, device=None, **additional_parameters):
+        """Fit one student on a blend of the hard labels and this ensemble's probabilities
+        (:func:`gentun_amd.models.cnn_distill.distill`). ``genes=None``: the first member's genes."""
+        from .cnn_distill import distill
+        return distill(self, x, y_onehot, dict(self.members[0].genes) if genes is None else genes, alpha=alpha,
+                       temperature=temperature, device=device, **additional_parameters)
+
     def hip_predictor(self, device, batch=256):
         """The cached :class:`HipEnsemblePredictor` of (device, rows per launch). The rows per launch are
         ``predict_batch(batch)`` lowered by the executor's rule for evaluation twins (``EVAL_TWIN_BUDGET``

@@ -151,6 +151,11 @@ class HipPopJob(FoldJob):
         if cfg.dtype not in K.PREC:
             raise ValueError("HIP backend precision must be one of {}".format(sorted(K.PREC)))
         self.layout = "nhwc8f" if cfg.dtype == "fp32" else "nhwc8"
+        if getattr(cfg, "dp_group", None) is not None and (
+                kw.get("soft_targets") is not None or float(getattr(cfg, "label_smoothing", 0.0) or 0.0) > 0.0):
+            raise ValueError("soft targets (label_smoothing / soft_targets) with dp_group are not supported by the "
+                             "HIP executor (the torch executor supports it); train without data parallelism or "
+                             "on the hard labels")
         # zero-padded storage of a slightly-smaller-than-power-of-two image (MNIST 28 x 28 -> 32 x 32):
         # every stage then runs the shape-specialised kernels (cnn_kernels.padded_hw)
         p0 = plan if plan is not None else kw["members"][0][0]
@@ -672,6 +677,17 @@ class HipPopJob(FoldJob):
         hd.prec = prec
         hd.dHp = self.dHp.data_ptr()
         self.head_args = hd
+        # soft targets (cnn_engine.py "The target row"): the training step's head launch becomes gt_head_soft
+        # over the same buffers; evaluation keeps gt_head on the hard labels. Off: nothing is built.
+        self.head_soft_args = None
+        if self.soft is not None or self.smooth_on_off is not None:
+            hs = K.HeadSoftArgs()
+            hs.head = hd                         # by value
+            if self.soft is not None:
+                hs.soft, hs.t_on, hs.t_off = self.soft.data_ptr(), 1.0, 0.0
+            else:
+                hs.soft, hs.t_on, hs.t_off = 0, float(self.smooth_on_off[0]), float(self.smooth_on_off[1])
+            self.head_soft_args = hs
         dd = K.DenseDgradArgs()
         dd.dH, dd.wt, dd.dx = self.dH.data_ptr(), 0, self.grad[self.last].data_ptr()
         dd.dHp = self.dHp.data_ptr()
@@ -967,8 +983,9 @@ class HipPopJob(FoldJob):
         if self.aug_args is not None:
             plan.append(("k", "gt_augment", (self.aug_args,), main, "augment"))
         plan += self._fwd_plan(self.train_fwd_ops)
-        plan += [("k", "gt_dense_fwd", (self.dense_fwd_args,), main, "dense_fwd"),
-                 ("k", "gt_head", (self.head_args,), main, "head"),
+        head = ("k", "gt_head", (self.head_args,), main, "head") if self.head_soft_args is None else \
+            ("k", "gt_head_soft", (self.head_soft_args,), main, "head_soft")
+        plan += [("k", "gt_dense_fwd", (self.dense_fwd_args,), main, "dense_fwd"), head,
                  ("k", "gt_dense_dgrad", (self.dense_dgrad_args,), main, "dense_dgrad")]   # reads W1 before its update
         side2 = self.side2
         nev = [0]

@@ -158,6 +158,12 @@ class HeadArgs(C.Structure):
                 ("prec", I), ("valid", P), ("valid_norm", P), ("dHp", P)]
 
 
+class HeadSoftArgs(C.Structure):
+    """csrc/hip/cnn_dense.hip HeadSoftArgs: the training head on soft targets (gt_head_soft) -- HeadArgs by
+    value, then the target table ``[N][C]`` fp32 (0: label smoothing with the two values that follow)."""
+    _fields_ = [("head", HeadArgs), ("soft", P), ("t_on", C.c_float), ("t_off", C.c_float)]
+
+
 class HeadPredictArgs(C.Structure):
     """csrc/hip/cnn_dense.hip HeadPredictArgs: logits and probabilities of every row (gt_head_predict)."""
     _fields_ = [("plog", P), ("b2", P), ("logits", P), ("proba", P), ("G", I), ("B", I), ("Up", I), ("C", I)]
@@ -298,7 +304,7 @@ PROG_OPS = {"record": 0, "wait": 1, "gt_step_begin": 2, "gt_conv_fwd": 3, "gt_co
             "gt_wgrad_reduce": 5, "gt_bn_fwd": 6, "gt_bn_bwd": 7, "gt_dense_fwd": 8, "gt_head": 9,
             "gt_dense_dgrad": 10, "gt_dense_wgrad_adam": 11, "gt_adam_segments": 12, "gt_pool_fwd": 13,
             "gt_pool_fwd_mask": 14, "gt_pool_bwd_mask": 15, "gt_wino_wtrans": 16,
-            "gt_conv_wfrag": 17, "gt_augment": 18}
+            "gt_conv_wfrag": 17, "gt_head_soft": 18, "gt_augment": 19}
 
 
 class AugArgs(C.Structure):
@@ -338,6 +344,10 @@ def lib():
         L.gt_augment.restype = I
         L.gt_sizeof_aug_args.restype = C.c_size_t
         assert L.gt_sizeof_aug_args() == C.sizeof(AugArgs), "AugArgs ABI mismatch"
+        L.gt_head_soft.argtypes = [C.POINTER(HeadSoftArgs), P]
+        L.gt_head_soft.restype = I
+        L.gt_sizeof_head_soft_args.restype = C.c_size_t
+        assert L.gt_sizeof_head_soft_args() == C.sizeof(HeadSoftArgs), "HeadSoftArgs ABI mismatch"
         L.gt_head_predict.argtypes = [C.POINTER(HeadPredictArgs), P]
         L.gt_head_predict.restype = I
         L.gt_sizeof_head_predict_args.restype = C.c_size_t

@@ -235,7 +235,8 @@ def _settings_key(model):
             c.epochs, c.learning_rate, c.batch_size, c.dropout, c.loss, c.dtype, c.seed, c.optimizer, c.momentum,
             getattr(c, "reset", None), getattr(c, "batching", None), getattr(c, "batch_norm", None),
             model.nodes, model.input_shape, model.kernels_per_layer, model.kernel_sizes, model.dense_units,
-            model.classes, tuple(sorted((getattr(c, "augment", None) or {}).items())))
+            model.classes, tuple(sorted((getattr(c, "augment", None) or {}).items())),
+            float(getattr(c, "label_smoothing", 0.0) or 0.0))
 
 
 def _check_shared_settings(chunk):

@@ -18,6 +18,7 @@
 #   bash tools/gpu.sh cnn-predict             CnnClassifier.predict: HIP predictor at 32 / 256 rows per launch vs stock torch on the GPU (ROWS= REPS=)
 #   bash tools/gpu.sh cnn-ensemble            CnnEnsemble.predict: one k-group launch set vs k predictors one by one vs stock torch; fit_ensemble vs k fits (ROWS= REPS= K= FIT_ROWS=)
 #   bash tools/gpu.sh cnn-augment             TrainConfig.augment: step time off / on (and the parent tree in ab_old/), gt_augment's kernel time (GROUPS_LIST= REPS= PROF_GROUPS= OUT=)
+#   bash tools/gpu.sh cnn-distill             soft targets: step time of the parent tree (ab_old/) / off / label_smoothing / a target table, the head kernels' time from a kernel trace run of its own, the distillation record (GROUPS_LIST= REPS= PROF_GROUPS= OUT= ACC=0)
 #   bash tools/gpu.sh cnn-tta                 predict(tta=...): views and mean on the device vs V plain HIP predicts combined in numpy vs stock torch, classifier and k-ensemble (ROWS= FIT_ROWS= K= REPS= OUT=)
 #   bash tools/gpu.sh cnn-occlusion           occlusion(): copies built and packed on the device vs occlusion_views in numpy + plain HIP predicts vs stock torch, classifier and k-ensemble (ROWS= FIT_ROWS= K= REPS= OUT= TIME=)
 #   bash tools/gpu.sh cnn-gradcam             gradcam(): forward + gt_head_gradcam vs plain HIP predict (the floor) vs stock-torch autograd vs occlusion(patch=4), classifier and k-ensemble; the new kernels' device time by events and by a kernel trace run of its own (ROWS= OCC_ROWS= FIT_ROWS= K= REPS= OUT= TIME=)
@@ -185,6 +186,23 @@ cnn-augment)
   find /tmp/prof_aug -name "*kernel_stats.csv" -exec cp {} $out/kernel_stats.csv \; &&
   grep -E "Name|augment" $out/kernel_stats.csv | cut -c1-300; rc=$?
   [ $rc -eq 0 ] || tail -5 $out/bench.err $out/prof.log 2>/dev/null
+  exit $rc ;;
+cnn-distill)
+  # step time on hard labels / smoothed labels / a target table (and in ab_old/, the built parent tree, when it is
+  # there), then the head kernels' own time from a kernel trace of one child run of its own, then the
+  # distillation record; files are kept under $OUT
+  out=${OUT:-/tmp/cnn_distill}; heartbeat; mkdir -p $out; rocprof_env; rm -rf /tmp/prof_distill
+  parent=""; [ -d ab_old/gentun_amd/_native ] && parent="--parent ab_old"
+  timeout -k 10 ${TIME:-900} python -u tools/bench_distill.py --groups ${GROUPS_LIST:-25,80} --reps ${REPS:-5} $parent \
+    > $out/bench.json 2> $out/bench.err &&
+  cut -c1-4000 $out/bench.json &&
+  timeout -k 10 300 rocprofv3 --kernel-trace --stats -d /tmp/prof_distill -o run --output-format csv -- \
+    python3 tools/bench_distill.py --child .:${PROF_GROUPS:-25}:table > $out/prof.log 2>&1 &&
+  find /tmp/prof_distill -name "*kernel_stats.csv" -exec cp {} $out/kernel_stats.csv \; &&
+  grep -E "Name|head_" $out/kernel_stats.csv | cut -c1-300 &&
+  { [ "${ACC:-1}" = 0 ] || { timeout -k 10 ${ACC_TIME:-600} python -u tools/bench_distill.py --accuracy \
+    > $out/accuracy.json 2> $out/accuracy.err && cut -c1-3000 $out/accuracy.json; }; }; rc=$?
+  [ $rc -eq 0 ] || tail -5 $out/bench.err $out/prof.log $out/accuracy.err 2>/dev/null
   exit $rc ;;
 cnn-tta)
   # the result line is printed; the files are kept under $OUT
