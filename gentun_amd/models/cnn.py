@@ -220,3 +220,12 @@ class GeneticCnnModel(GentunModel):
             raise RuntimeError("GeneticCnnModel.gradcam before fit()")
         kwargs.setdefault("device", self.device)
         return self.fitted.gradcam(x, **kwargs)
+
+    def predict_mc(self, x, **kwargs):
+        """``self.fitted.predict_mc`` on this model's device and with this model's ``dropout_probability``
+        unless ``device`` / ``dropout`` say otherwise."""
+        if self.fitted is None:
+            raise RuntimeError("GeneticCnnModel.predict_mc before fit()")
+        kwargs.setdefault("device", self.device)
+        kwargs.setdefault("dropout", self.dropout_probability)
+        return self.fitted.predict_mc(x, **kwargs)

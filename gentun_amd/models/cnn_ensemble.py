@@ -24,9 +24,9 @@ import math
 import numpy as np
 import torch
 
-from .cnn_fitted import (CnnClassifier, TtaState, cam_check, cam_check_hip, cam_upsample, gradcam_state,
-                         occlusion_by_views, occlusion_fill, occlusion_grid, occlusion_state, occlusion_targets,
-                         predict_batch, tta_views)
+from .cnn_fitted import (CnnClassifier, TtaState, cam_check, cam_check_hip, cam_upsample, gradcam_state, mc_check,
+                         mc_check_hip, mc_result, mc_state, mc_statistics, occlusion_by_views, occlusion_fill,
+                         occlusion_grid, occlusion_state, occlusion_targets, predict_batch, tta_views)
 
 FORMAT = "gentun-cnn-ensemble/1"
 OUTPUTS = ("proba", "label", "votes", "vote_label", "member_proba", "member_logits")
@@ -272,6 +272,27 @@ class CnnEnsemble(object):
         cam = cam_upsample(res[0], self.input_shape[:2]) if upsample else res[0]
         return (cam, {"target": res[1], "base": res[2]}) if return_info else cam
 
+    def predict_mc(self, x, samples=32, dropout=0.5, seed=0, device=None, batch=256, backend=None,
+                   return_samples=False):
+        """Monte-Carlo dropout of the ensemble (``CnnClassifier.predict_mc``): every member draws ``samples``
+        masks of its own (member index ``m`` keys ``utils.rng.mc_masks(seed, m, ...)``) and the statistics are
+        those of all ``k * samples`` probability vectors under the members' weights
+        (``cnn_fitted.mc_statistics``): ``std`` holds the spread inside the members and between them.
+        ``return_samples=True`` adds ``samples`` ``[n, k, samples, classes]``."""
+        samples, dropout, seed, batch = mc_check(samples, dropout, seed, batch)
+        x = self.members[0]._check_x(x)
+        dev = torch.device("cpu" if device is None else device)
+        if backend is None:
+            backend = "hip" if dev.type == "cuda" else "torch"
+        if backend == "hip":
+            mc_check_hip(self.classes)
+            return self.hip_predictor(dev, batch).predict_mc(x, samples, dropout, seed, bool(return_samples))
+        if backend != "torch":
+            raise ValueError("unknown backend {!r}".format(backend))
+        p = np.stack([m._torch_mc(x, i, samples, dropout, seed, dev, batch, torch.float32)
+                      for i, m in enumerate(self.members)])
+        return mc_result(mc_statistics(p, self.weights), p if return_samples else None)
+
     def distill(self, x, y_onehot, genes=None, alpha=0.5, temperature=1.0, device=None, **additional_parameters):
         """Fit one student on a blend of the hard labels and this ensemble's probabilities
         (:func:`gentun_amd.models.cnn_distill.distill`). ``genes=None``: the first member's genes."""
@@ -352,6 +373,7 @@ class HipEnsemblePredictor(object):
         self._occ = {}               # (patch, stride, fill, score) -> OcclusionState, created on first use
         self._cam = {}               # (score, relu) -> GradcamState, created on first use
         self._cam_wbar = None        # W1 summed over the real pixels (cam_wbar), on the first Grad-CAM request
+        self._mc = None              # McState, created on the first Monte-Carlo dropout request
 
     def _host(self, ens, EB):
         from . import cnn_engine as E
@@ -404,6 +426,11 @@ class HipEnsemblePredictor(object):
         """``(map, target, base)`` of validated arguments (``CnnEnsemble.gradcam``) over the ``k`` members and
         their weights."""
         return gradcam_state(self, score, relu, self.k, self.weight).run(self, x, target)
+
+    def predict_mc(self, x, samples, dropout, seed, return_samples):
+        """The dict of validated arguments (``CnnEnsemble.predict_mc``) over the ``k`` members and their
+        weights."""
+        return mc_state(self, self.k, self.weight).run(self, x, samples, dropout, seed, return_samples)
 
     def run(self, x, members=False, views=None):
         """``x`` [n, H, W, C] host fp32 -> ``{"proba", "votes"}`` (+ ``"member_proba"``, ``"member_logits"``)

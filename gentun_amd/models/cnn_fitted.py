@@ -109,6 +109,95 @@ def tta_combine(per_view):
     return (acc * (one(1) / one(len(per_view)))).astype(acc.dtype, copy=False)
 
 
+MC_MAX_SAMPLES = 64          # MC_MAXT of csrc/hip/cnn_head_mc.hip
+MC_OUTPUTS = ("proba", "std", "entropy", "mutual_info", "label")
+
+
+def mc_check(samples, dropout, seed, batch):
+    """The validated ``(samples, dropout, seed, batch)`` of a Monte-Carlo dropout request, before any forward
+    runs: ``samples`` an int in ``1..64``, ``dropout`` a float in ``[0, 1)``, ``seed`` an int in ``[0, 2^32)``,
+    ``batch`` a positive int (``predict``'s rule). ``ValueError`` on anything else."""
+    if not _is_int(samples) or not 1 <= int(samples) <= MC_MAX_SAMPLES:
+        raise ValueError("predict_mc: samples must be an integer in [1, {}], got {!r}".format(MC_MAX_SAMPLES, samples))
+    if isinstance(dropout, (bool, np.bool_)) or not isinstance(dropout, (int, float, np.integer, np.floating)) \
+            or not 0.0 <= float(dropout) < 1.0:
+        raise ValueError("predict_mc: dropout must be a number in [0, 1), got {!r}".format(dropout))
+    if not _is_int(seed) or not 0 <= int(seed) < 2 ** 32:
+        raise ValueError("predict_mc: seed must be an integer in [0, 2^32), got {!r}".format(seed))
+    if not _is_int(batch) or int(batch) < 1:
+        raise ValueError("batch must be a positive integer")
+    return int(samples), float(dropout), int(seed), int(batch)
+
+
+def mc_keep_scale(dropout):
+    """``fp32(1) / (fp32(1) - fp32(dropout))``, training's ``keep_scale``."""
+    return np.float32(1) / (np.float32(1) - np.float32(dropout))
+
+
+def mc_entropy(p):
+    """``-sum_c p ln p`` over the last axis in the dtype of ``p``, with ``0 ln 0 = 0``."""
+    p = np.asarray(p)
+    safe = np.where(p > 0, p, p.dtype.type(1))
+    return -(p * np.log(safe)).sum(-1, dtype=p.dtype)
+
+
+def mc_statistics(p, weights):
+    """The Monte-Carlo dropout statistics of sample probabilities ``p [k, n, T, C]`` under normalised member
+    weights ``[k]``, in the dtype of ``p`` (fp32: what both backends return; the HIP kernel forms the same
+    quantities in the same arrangement on the device):
+
+    per member the mean over ``t``, shifted by the first sample (``p_0 + mean_t(p_t - p_0)``: exact when every
+    sample is the same), and the two-pass variance around it; ``proba = sum_m w_m mean_m`` in member order;
+    ``std = sqrt(sum_m w_m (var_m + (mean_m - proba)^2))``, the population variance over all ``(m, t)`` by the
+    law of total variance; ``entropy = H(proba)``; ``expected_entropy = sum_m w_m mean_t H(p_{m,t})``;
+    ``mutual_info = max(entropy - expected_entropy, 0)`` by :func:`mc_mutual_info`; ``label`` the first maximum
+    of ``proba``."""
+    p = np.asarray(p)
+    ft = p.dtype.type
+    w = np.asarray(weights, p.dtype)
+    inv_t = ft(1) / ft(p.shape[2])
+    mean = p[:, :, 0] + (p - p[:, :, :1]).sum(2, dtype=p.dtype) * inv_t
+    var = ((p - mean[:, :, None]) ** 2).sum(2, dtype=p.dtype) * inv_t
+    h = mc_entropy(p)                                                    # [k, n, T]
+    hmean = h[:, :, 0] + (h - h[:, :, :1]).sum(2, dtype=p.dtype) * inv_t
+    proba = w[0] * mean[0]
+    for g in range(1, p.shape[0]):
+        proba = proba + w[g] * mean[g]
+    tv, eh = np.zeros_like(proba), np.zeros(p.shape[1], p.dtype)
+    for g in range(p.shape[0]):
+        tv = tv + w[g] * (var[g] + (mean[g] - proba) ** 2)
+        eh = eh + w[g] * hmean[g]
+    entropy = mc_entropy(proba)
+    return {"proba": proba, "std": np.sqrt(tv), "entropy": entropy, "expected_entropy": eh,
+            "mutual_info": mc_mutual_info(p, w), "label": np.argmax(proba, axis=1).astype(np.int64)}
+
+
+def mc_mutual_info(p, weights):
+    """``max(H(sum_m w_m mean_t p_{m,t}) - sum_m w_m mean_t H(p_{m,t}), 0)`` of sample probabilities
+    ``p [k, n, T, C]``, both entropies taken in fp64 from the samples as they are and the difference rounded once
+    to the dtype of ``p``. The difference of the two fp32 entropies would carry their representation error,
+    ``2^-23`` of an entropy near 1, which is 2e-5 of a mutual information of 5e-3; errors of the samples
+    themselves move both entropies alike and cancel."""
+    p64, w = np.asarray(p, np.float64), np.asarray(weights, np.float64)
+    proba = np.tensordot(w, p64.mean(2), 1)
+    expected = np.tensordot(w, mc_entropy(p64).mean(2), 1)
+    return np.maximum(mc_entropy(proba) - expected, 0.0).astype(np.asarray(p).dtype)
+
+
+def mc_result(stats, samples):
+    """What ``predict_mc`` returns from :func:`mc_statistics`-shaped arrays (``samples [k, n, T, C]`` or None)."""
+    out = {name: stats[name] for name in MC_OUTPUTS}
+    if samples is not None:
+        out["samples"] = np.ascontiguousarray(np.transpose(samples, (1, 0, 2, 3)))       # [n, k, T, C]
+    return out
+
+
+def mc_check_hip(classes):
+    """The ``ValueError`` of more classes than the HIP head kernels take, before a predictor is built."""
+    if classes > 16:
+        raise ValueError("HIP head kernel supports at most 16 classes")
+
+
 OCC_MAX_CELLS = 4096         # OCC_MAX_CELLS of csrc/hip/cnn_occlude.hip
 OCC_SCORES = ("proba", "logit")
 
@@ -502,6 +591,37 @@ class CnnClassifier(object):
         cam = cam_upsample(res[0], self.input_shape[:2]) if upsample else res[0]
         return (cam, {"target": res[1], "base": res[2]}) if return_info else cam
 
+    def predict_mc(self, x, samples=32, dropout=0.5, seed=0, device=None, batch=256, backend=None,
+                   return_samples=False):
+        """Monte-Carlo dropout (Gal & Ghahramani) of ``x`` ``[n, H, W, C]`` (or one image): ``samples`` forward
+        passes of the dense head with the dropout between its two layers switched on at rate ``dropout`` (model
+        files do not record the rate: the reference's 0.5 unless given), everything before it in evaluation
+        mode. Returns a dict of fp32 arrays (:func:`mc_statistics`): ``proba [n, classes]``, the mean
+        probability; ``std [n, classes]``, its standard deviation over the samples; ``entropy [n]`` of the mean;
+        ``mutual_info [n]`` (BALD), the entropy minus the samples' mean entropy (:func:`mc_mutual_info`); ``label`` int64 ``[n]``, the
+        first maximum of ``proba``. ``return_samples=True`` adds ``samples`` ``[n, 1, samples, classes]``.
+
+        The mask of sample ``t``, image ``n`` (the index in ``x``, so chunking changes no bit) and hidden unit
+        ``u`` is ``utils.rng.mc_masks(seed, 0, ...)``; a kept unit is ``h[u] * keep_scale``. With ``dropout=0``
+        every sample is the plain forward.
+
+        ``device`` / ``backend`` / ``batch`` as in :meth:`predict`: the CPU or ``backend="torch"`` runs the
+        stock-torch forward up to the hidden row once and the second dense layer per sample; a ``cuda`` device
+        runs the HIP predictor's forward and ``gt_head_mc`` (csrc/hip/cnn_head_mc.hip), which draws the masks on
+        the device and writes only the statistics."""
+        samples, dropout, seed, batch = mc_check(samples, dropout, seed, batch)
+        x = self._check_x(x)
+        dev = torch.device("cpu" if device is None else device)
+        if backend is None:
+            backend = "hip" if dev.type == "cuda" else "torch"
+        if backend == "hip":
+            mc_check_hip(self.classes)
+            return self.hip_predictor(dev, batch).predict_mc(x, samples, dropout, seed, bool(return_samples))
+        if backend != "torch":
+            raise ValueError("unknown backend {!r}".format(backend))
+        p = self._torch_mc(x, 0, samples, dropout, seed, dev, batch, torch.float32)[None]
+        return mc_result(mc_statistics(p, np.ones(1, np.float32)), p if return_samples else None)
+
     def hip_predictor(self, device, batch=256):
         """The cached :class:`HipPredictor` of (device, rows per launch)."""
         dev = torch.device(device)
@@ -549,6 +669,40 @@ class CnnClassifier(object):
         feat = A.reshape(1, A.shape[0], -1)
         h = F.relu(torch.baddbmm(P["dense1.b"][None, None, :], feat, P["dense1.w"][None]))
         return torch.baddbmm(P["dense2.b"][None, None, :], h, P["dense2.w"][None])[0]
+
+    def _torch_hidden(self, A, P):
+        """The last feature map [n, C_last, hr, wr] -> the hidden row ``h = relu(feat W1 + b1)`` [n, units]."""
+        feat = A.reshape(1, A.shape[0], -1)
+        return F.relu(torch.baddbmm(P["dense1.b"][None, None, :], feat, P["dense1.w"][None]))[0]
+
+    def _torch_mc(self, x, member, samples, dropout, seed, dev, batch, dtype):
+        """The Monte-Carlo dropout samples ``p [n, samples, classes]`` by stock torch in ``dtype`` (fp32, or
+        fp64: the tests' reference) as member ``member`` of an ensemble: the forward of :meth:`_torch_predict`
+        up to the hidden row once per chunk (rows filled with zero images to a multiple of 32), then per sample
+        the masked row (``utils.rng.mc_masks``), the second dense layer at the chunk's padded rows and the
+        softmax."""
+        from ..utils.rng import mc_masks
+        P = self._tensors(dev, dtype)
+        n = x.shape[0]
+        h, w, c = self.input_shape
+        ftype = np.float64 if dtype == torch.float64 else np.float32
+        scale = float(mc_keep_scale(dropout))
+        out = np.empty((n, samples, self.classes), ftype)
+        with torch.no_grad():
+            for s in range(0, n, batch):
+                m = min(batch, n - s)
+                rows = (m + 31) // 32 * 32
+                buf = np.zeros((rows, c, h, w), np.float32)
+                buf[:m] = x[s:s + m].transpose(0, 3, 1, 2)
+                hid = self._torch_hidden(self._torch_features(torch.from_numpy(buf).to(device=dev, dtype=dtype), P), P)
+                keep = torch.from_numpy(mc_masks(seed, member, samples, np.arange(s, s + rows), self.dense_units,
+                                                 dropout)).to(dev)
+                kept = hid * torch.tensor(scale, dtype=dtype, device=dev)
+                for t in range(samples):
+                    hm = torch.where(keep[t], kept, torch.zeros_like(kept))
+                    lg = torch.baddbmm(P["dense2.b"][None, None, :], hm[None], P["dense2.w"][None])[0, :m]
+                    out[s:s + m, t] = torch.softmax(lg, dim=-1).cpu().numpy()
+        return out
 
     def _torch_gradcam(self, x, target, score, relu, dev, batch, dtype):
         """``(map [n, hr, wr], target int64 [n], base [n])`` by stock torch in ``dtype`` (fp32, or fp64: the
@@ -952,6 +1106,84 @@ def gradcam_state(pred, score, relu, G, weight):
     return st
 
 
+class McState(object):
+    """What a HIP predictor (``HipPredictor`` or ``HipEnsemblePredictor``) adds for Monte-Carlo dropout: the
+    outputs of one chunk of ``EB`` rows and one argument struct of ``gt_head_mc`` over the predictor's own
+    buffers (the hidden activations ``gt_dense_fwd`` wrote in evaluation mode, the fp32 masters of ``W2`` and
+    ``b2``, the members' weights). The predictor's job, evaluation launches, staging tensor and ``upload`` are
+    used as they are, at ``EB`` rows."""
+
+    def __init__(self, pred, G, weight):
+        K, job, EB, dev, C = pred.K, pred.job, pred.EB, pred.device, pred.classes
+        self.G, self.weight = G, weight
+        self.proba = torch.empty((EB, C), dtype=torch.float32, device=dev)
+        self.std = torch.empty_like(self.proba)
+        self.entropy = torch.empty(EB, dtype=torch.float32, device=dev)
+        self.expected = torch.empty_like(self.entropy)
+        self.mutual = torch.empty_like(self.entropy)
+        self.label = torch.empty(EB, dtype=torch.int32, device=dev)
+        self.samples = None                      # [EB][G][T][C], allocated when asked for
+        a = K.HeadMcArgs()
+        a.h, a.w2, a.b2, a.weight = pred.df.out, pred.df.w2, job.views["b2"][0].data_ptr(), weight.data_ptr()
+        a.proba, a.std = self.proba.data_ptr(), self.std.data_ptr()
+        a.entropy, a.expected_entropy = self.entropy.data_ptr(), self.expected.data_ptr()
+        a.mutual_info, a.label = self.mutual.data_ptr(), self.label.data_ptr()
+        a.G, a.B, a.Up, a.Ur, a.C = G, EB, job.Up, job.members[0][0].dense_units, C
+        a.prec = pred.df.prec
+        self.head = a
+
+    def run(self, pred, x, samples, dropout, seed, return_samples):
+        """``x`` [n, H, W, C] host fp32 -> the dict of ``predict_mc`` as host arrays: per chunk of ``EB`` images
+        one upload, the evaluation launches, ``gt_dense_fwd`` and ``gt_head_mc`` with ``n0`` the chunk's offset;
+        the results gather on the device and are read back once."""
+        from ..utils.rng import mc_threshold
+        job, K, a = pred.job, pred.K, self.head
+        n, EB, dev, C, G, T = x.shape[0], pred.EB, pred.device, pred.classes, self.G, samples
+        a.T, a.thr, a.seed = T, mc_threshold(dropout), seed
+        a.keep_scale, a.inv_T = float(mc_keep_scale(dropout)), float(np.float32(1) / np.float32(T))
+        with torch.cuda.device(dev):
+            a.samples = 0
+            if return_samples:
+                if self.samples is None or self.samples.numel() < EB * G * T * C:
+                    self.samples = torch.empty(EB * G * T * C, dtype=torch.float32, device=dev)
+                a.samples = self.samples.data_ptr()
+                smp = torch.empty((n, G, T, C), dtype=torch.float32, device=dev)
+            proba = torch.empty((n, C), dtype=torch.float32, device=dev)
+            std = torch.empty_like(proba)
+            ent = torch.empty(n, dtype=torch.float32, device=dev)
+            mi = torch.empty_like(ent)
+            label = torch.empty(n, dtype=torch.int32, device=dev)
+            for s in range(0, n, EB):
+                m = min(EB, n - s)
+                pred.upload(x[s:s + m])
+                a.m, a.n0 = m, s
+                st = job._stream()
+                job._run_fwd(st, pred.ops)
+                K.check(job.L.gt_dense_fwd(pred.df, st), "dense_fwd(mc)")
+                K.check(job.L.gt_head_mc(a, st), "head_mc")
+                proba[s:s + m].copy_(self.proba[:m])
+                std[s:s + m].copy_(self.std[:m])
+                ent[s:s + m].copy_(self.entropy[:m])
+                mi[s:s + m].copy_(self.mutual[:m])
+                label[s:s + m].copy_(self.label[:m])
+                if return_samples:
+                    smp[s:s + m].copy_(self.samples[:m * G * T * C].view(m, G, T, C))
+            out = {"proba": proba.cpu().numpy(), "std": std.cpu().numpy(), "entropy": ent.cpu().numpy(),
+                   "mutual_info": mi.cpu().numpy(),
+                   "label": label.cpu().numpy().astype(np.int64)}
+            if return_samples:
+                out["samples"] = smp.cpu().numpy()
+        return out
+
+
+def mc_state(pred, G, weight):
+    """The cached :class:`McState` of a predictor (its ``_mc``), built on the first request."""
+    if pred._mc is None:
+        with torch.cuda.device(pred.device):
+            pred._mc = McState(pred, G, weight)
+    return pred._mc
+
+
 class HipPredictor(object):
     """Forward-only HIP launches of one fitted model at ``EB`` rows per launch.
 
@@ -1003,6 +1235,7 @@ class HipPredictor(object):
         self._one = None             # the one member's weight 1.0 on the device, for the occlusion head
         self._cam = {}               # (score, relu) -> GradcamState, created on first use
         self._cam_wbar = None        # W1 summed over the real pixels (cam_wbar), on the first Grad-CAM request
+        self._mc = None              # McState, created on the first Monte-Carlo dropout request
 
     def forward(self):
         """The launches of one chunk on the current stream: staging tensor -> ``logits`` / ``proba``."""
@@ -1042,6 +1275,12 @@ class HipPredictor(object):
         if self._one is None:
             self._one = torch.ones(1, dtype=torch.float32, device=self.device)
         return gradcam_state(self, score, relu, 1, self._one).run(self, x, target)
+
+    def predict_mc(self, x, samples, dropout, seed, return_samples):
+        """The dict of validated arguments (``CnnClassifier.predict_mc``): one member of weight 1.0."""
+        if self._one is None:
+            self._one = torch.ones(1, dtype=torch.float32, device=self.device)
+        return mc_state(self, 1, self._one).run(self, x, samples, dropout, seed, return_samples)
 
     def run(self, x, views=None):
         """``x`` [n, H, W, C] host fp32 -> (logits, proba) host fp32 ``[n, classes]``; with ``views`` (a tuple

@@ -216,6 +216,19 @@ class HeadGradcamArgs(C.Structure):
                 ("relu", I), ("inv_n", C.c_float)]
 
 
+class HeadMcArgs(C.Structure):
+    """csrc/hip/cnn_head_mc.hip HeadMcArgs: Monte-Carlo dropout statistics of every image of a launch
+    (gt_head_mc)."""
+    _fields_ = [("h", P), ("w2", P), ("b2", P), ("weight", P), ("proba", P), ("std", P), ("entropy", P),
+                ("expected_entropy", P), ("mutual_info", P), ("label", P), ("samples", P), ("G", I), ("B", I),
+                ("Up", I), ("Ur", I), ("C", I), ("T", I), ("m", I), ("prec", I), ("thr", C.c_uint), ("seed", C.c_uint),
+                ("n0", C.c_uint),
+                ("keep_scale", C.c_float), ("inv_T", C.c_float)]
+
+
+MC_MAX_SAMPLES = 64     # samples of one Monte-Carlo dropout request at most (csrc/hip/cnn_head_mc.hip MC_MAXT)
+
+
 OCC_MAX_CELLS = 4096    # cells of one occlusion grid at most (csrc/hip/cnn_occlude.hip OCC_MAX_CELLS)
 
 
@@ -376,6 +389,10 @@ def lib():
         L.gt_head_gradcam.restype = I
         L.gt_sizeof_head_gradcam_args.restype = C.c_size_t
         assert L.gt_sizeof_head_gradcam_args() == C.sizeof(HeadGradcamArgs), "HeadGradcamArgs ABI mismatch"
+        L.gt_head_mc.argtypes = [C.POINTER(HeadMcArgs), P]
+        L.gt_head_mc.restype = I
+        L.gt_sizeof_head_mc_args.restype = C.c_size_t
+        assert L.gt_sizeof_head_mc_args() == C.sizeof(HeadMcArgs), "HeadMcArgs ABI mismatch"
         L.gt_occlude_views.argtypes = [C.POINTER(OccludeArgs), P]
         L.gt_occlude_views.restype = I
         L.gt_sizeof_occlude_args.restype = C.c_size_t

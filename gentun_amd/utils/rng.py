@@ -100,3 +100,23 @@ def aug_draws(key, step, rows, shift, flip):
     dx = (r1 % span).astype(np.int64) - int(shift)
     fl = (r2 >> np.uint64(31)).astype(np.int64) if flip else np.zeros(r2.shape, np.int64)
     return dy, dx, fl
+
+
+MC_KEY = 0x4D434452         # hash4 counter of the Monte-Carlo dropout member key ("MCDR")
+
+
+def mc_threshold(dropout):
+    """``uint32(dropout * 2^32)``: a unit is kept iff its draw is at least this (``dense_fwd_epilogue``'s rule)."""
+    return int(float(dropout) * 4294967296.0) & _M32
+
+
+def mc_masks(seed, member, samples, rows, units, dropout):
+    """Keep masks of Monte-Carlo dropout (csrc/hip/cnn_head_mc.hip), bool ``[samples, len(rows), units]``:
+    sample ``t``, image index ``n = rows[i]`` and unit ``u`` are kept iff
+    ``hash4(hash4(seed, member, MC_KEY, 0), t, n, u) >= mc_threshold(dropout)``."""
+    import numpy as np
+    key = hash4(int(seed), int(member), MC_KEY, 0)
+    t = np.arange(int(samples), dtype=np.uint64)[:, None, None]
+    n = np.asarray(rows, dtype=np.uint64).reshape(1, -1, 1)
+    u = np.arange(int(units), dtype=np.uint64)[None, None, :]
+    return hash4(key, t, n, u) >= np.uint64(mc_threshold(dropout))

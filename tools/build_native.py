@@ -50,6 +50,14 @@ TARGETS = {
 }
 
 
+# extra compile flags of single translation units (by base name), part of the source hash: the Monte-Carlo
+# dropout head is built without packed fp32 VALU ops (the host pass reports the device feature as unknown
+# and ignores it)
+HIP_EXTRA_FLAGS = {
+    "cnn_head_mc.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+}
+
+
 def _abs(p):
     return p if os.path.isabs(p) else os.path.join(ROOT, p)
 
@@ -61,6 +69,8 @@ def source_hash(name):
     h = hashlib.sha256()
     h.update(spec["kind"].encode())
     h.update(" ".join(_flags(spec["kind"])).encode())
+    if spec["kind"] == "hip":
+        h.update(repr(sorted(HIP_EXTRA_FLAGS.items())).encode())
     for f in sorted(set(_abs(x) for x in spec["sources"] + spec["deps"])):
         h.update(os.path.relpath(f, ROOT).encode())
         with open(f, "rb") as fh:
@@ -172,7 +182,7 @@ def _build_locked(name, spec, srcs, lib, verbose):
         for src in srcs:
             obj = os.path.join(objdir, os.path.basename(src) + ".o")
             objs.append(obj)
-            cmds.append(comp + ["-c", "-o", obj, src])
+            cmds.append(comp + HIP_EXTRA_FLAGS.get(os.path.basename(src), []) + ["-c", "-o", obj, src])
         from concurrent.futures import ThreadPoolExecutor
         jobs = max(1, min(len(cmds), int(os.environ.get("MAX_JOBS", "0")) or (os.cpu_count() or 4)))
         with ThreadPoolExecutor(jobs) as ex:
