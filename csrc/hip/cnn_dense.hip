@@ -955,6 +955,116 @@ __global__ void __launch_bounds__(256) head_gradcam_kernel(HeadGradcamArgs a) {
   }
 }
 
+// Saliency head (models/cnn_fitted.py SaliencyState): seeds the evaluation-mode backward chain with the
+// gradient of the target's score with respect to the hidden activations, for every member.
+struct HeadSaliencyArgs {
+  const float* plog;       // [G][Up/16][B][C] partial logits from dense_fwd (evaluation mode)
+  const float* b2;         // [G][C]
+  const float* weight;     // [G] fp32, normalised on the host
+  const void* hid;         // [G][B][Up] dense_fwd's output h = relu(z), bf16 or fp32 (prec)
+  const float* w2;         // [G][Up][C]
+  int* tgt;                // [m] target class per image; a negative entry is replaced by the image's label
+  float* base;             // [m] the score of the target
+  float* dH;               // [G][B][Up] what gt_dense_dgrad reads in fp32 mode
+  uint16_t* dHp;           // [planes][G][B][Up] head_bwd_kernel's bf16 planes of dH (3 in fp32 mode, else 1), or null
+  int G, B, Up, C;
+  int m;                   // rows b >= m get zero dH (and planes)
+  int prec, logit;
+};
+
+// One workgroup of 4 waves per row b < B. Phases (a) and (b) of head_gradcam_kernel, operation for operation:
+// the members' softmaxes, the label (first maximum of the combined probabilities), the base score, and per
+// member coef[c] and dH[u] = h[u] > 0 ? sum_c coef[c] * W2[u][c] : 0 (classes ascending, h > 0 off the bits).
+__global__ void __launch_bounds__(256) head_saliency_kernel(HeadSaliencyArgs a) {
+#pragma clang fp contract(off)
+  __shared__ float ps[ENS_MAXG][HEAD_MAXC];
+  __shared__ float ls[ENS_MAXG][HEAD_MAXC];
+  __shared__ float coef[HEAD_MAXC];
+  __shared__ int tsh;
+  const int b = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int C = a.C, nt = a.Up / 16;
+  const long ps_stride = (long)a.G * a.B * a.Up;
+  const int npl = a.prec ? GT_NPL_F32 : 1;
+  if (b >= a.m) {                                  // block-uniform: no barrier is skipped
+    for (int g = 0; g < a.G; ++g)
+      for (int u = tid; u < a.Up; u += 256) {
+        const long o = ((long)g * a.B + b) * a.Up + u;
+        a.dH[o] = 0.f;
+        if (a.dHp)
+          for (int p = 0; p < npl; ++p) a.dHp[p * ps_stride + o] = 0;
+      }
+    return;
+  }
+  for (int g = wave; g < a.G; g += 4) {
+    float lo, pr;
+    head_row_softmax(a.plog + ((long)g * nt * a.B + b) * C, a.b2 + (long)g * C, a.B, C, nt, lane, lo, pr);
+    if (lane < C) {
+      ps[g][lane] = pr;
+      ls[g][lane] = lo;
+    }
+  }
+  __syncthreads();
+  if (wave == 0) {
+    const float mean = lane < C ? ensemble_mean(a.weight, ps, a.G, lane) : 0.f;
+    const float score = a.logit ? (lane < C ? ensemble_mean(a.weight, ls, a.G, lane) : 0.f) : mean;
+    int t = a.tgt[b];
+    if (t < 0) {
+      float best = __shfl(mean, 0);
+      t = 0;
+#pragma unroll
+      for (int c = 1; c < HEAD_MAXC; ++c) {
+        const float v = __shfl(mean, c);
+        if (c < C && v > best) { best = v; t = c; }
+      }
+    }
+    t = min(t, C - 1);                             // see head_gradcam_kernel
+    const float s = __shfl(score, t);
+    if (lane == 0) {
+      a.tgt[b] = t;
+      a.base[b] = s;
+      tsh = t;
+    }
+  }
+  __syncthreads();
+  const int t = tsh;
+  for (int g = 0; g < a.G; ++g) {
+    if (tid < C) {
+      const float hot = tid == t ? 1.f : 0.f;
+      float cf = hot;
+      if (!a.logit) {
+        const float d = hot - ps[g][tid];
+        cf = ps[g][t] * d;
+      }
+      coef[tid] = cf;
+    }
+    __syncthreads();
+    for (int u = tid; u < a.Up; u += 256) {
+      const long o = ((long)g * a.B + b) * a.Up + u;
+      const float h = a.prec ? static_cast<const float*>(a.hid)[o] : bf2f(static_cast<const uint16_t*>(a.hid)[o]);
+      float v = 0.f;
+      if (__float_as_int(h) > 0) {
+        const float* w2 = a.w2 + ((long)g * a.Up + u) * C;
+        v = coef[0] * w2[0];
+        for (int c = 1; c < C; ++c) {
+          const float term = coef[c] * w2[c];
+          v = v + term;
+        }
+      }
+      a.dH[o] = v;
+      if (a.dHp) {
+        if (a.prec) {
+          uint16_t hq[3];
+          split3(v, hq);
+          a.dHp[o] = hq[0]; a.dHp[ps_stride + o] = hq[1]; a.dHp[2 * ps_stride + o] = hq[2];
+        } else {
+          a.dHp[o] = f2bf(v);
+        }
+      }
+    }
+    __syncthreads();                               // the next member's coef follows every reader
+  }
+}
+
 // (2) grid (ceil(Up/64), G): per 64-unit slice, dH = (dz W2^T) * scale * (h > 0),
 //     gb1 = sum_b dH, gW2 = h^T dz; block 0 also gb2 = sum_b dz.
 __global__ void __launch_bounds__(256) head_bwd_kernel(HeadArgs a) {
@@ -1620,6 +1730,18 @@ int gt_head_gradcam(const HeadGradcamArgs* a, hipStream_t stream) {
   return (int)hipGetLastError();
 }
 
+// One workgroup per row of the launch (rows >= m only clear their dH).
+int gt_head_saliency(const HeadSaliencyArgs* a, hipStream_t stream) {
+  if (!a) return -3;
+  if (a->C < 1 || a->C > HEAD_MAXC || a->G < 1 || a->G > ENS_MAXG || a->B < 1) return -1;
+  if (a->Up < 16 || a->Up % 16) return -2;
+  if (!a->plog || !a->b2 || !a->weight || !a->hid || !a->w2 || !a->tgt || !a->base || !a->dH) return -3;
+  if (a->m < 1 || a->m > a->B) return -4;
+  if ((a->prec != 0 && a->prec != 1) || (a->logit != 0 && a->logit != 1)) return -4;
+  hipLaunchKernelGGL(head_saliency_kernel, dim3((unsigned)a->B), dim3(256), 0, stream, *a);
+  return (int)hipGetLastError();
+}
+
 int gt_dense_dgrad(const DenseDgradArgs* a, hipStream_t stream) {
   if (a->Fp % 64 && a->Fp % 8) return -1;
   if (a->unpool_mask && (a->Cp % 8 || a->Hs % 2 || a->Ws % 2 || (long)(a->Hs / 2) * (a->Ws / 2) * a->Cp != a->Fp))
@@ -1669,6 +1791,7 @@ size_t gt_sizeof_head_tta_args() { return sizeof(HeadTtaArgs); }
 size_t gt_sizeof_head_occlusion_args() { return sizeof(HeadOcclusionArgs); }
 size_t gt_sizeof_cam_w1sum_args() { return sizeof(CamW1SumArgs); }
 size_t gt_sizeof_head_gradcam_args() { return sizeof(HeadGradcamArgs); }
+size_t gt_sizeof_head_saliency_args() { return sizeof(HeadSaliencyArgs); }
 size_t gt_sizeof_dense_dgrad_args() { return sizeof(DenseDgradArgs); }
 size_t gt_sizeof_dense_wgrad_args() { return sizeof(DenseWgradAdamArgs); }
 

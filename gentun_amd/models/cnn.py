@@ -221,6 +221,13 @@ class GeneticCnnModel(GentunModel):
         kwargs.setdefault("device", self.device)
         return self.fitted.gradcam(x, **kwargs)
 
+    def saliency(self, x, **kwargs):
+        """``self.fitted.saliency`` on this model's device unless ``device`` says otherwise."""
+        if self.fitted is None:
+            raise RuntimeError("GeneticCnnModel.saliency before fit()")
+        kwargs.setdefault("device", self.device)
+        return self.fitted.saliency(x, **kwargs)
+
     def predict_mc(self, x, **kwargs):
         """``self.fitted.predict_mc`` on this model's device and with this model's ``dropout_probability``
         unless ``device`` / ``dropout`` say otherwise."""

@@ -26,7 +26,8 @@ import torch
 
 from .cnn_fitted import (CnnClassifier, TtaState, cam_check, cam_check_hip, cam_upsample, gradcam_state, mc_check,
                          mc_check_hip, mc_result, mc_state, mc_statistics, occlusion_by_views, occlusion_fill,
-                         occlusion_grid, occlusion_state, occlusion_targets, predict_batch, tta_views)
+                         occlusion_grid, occlusion_state, occlusion_targets, predict_batch, saliency_check,
+                         saliency_check_hip, saliency_info, saliency_reduce, saliency_state, tta_views)
 
 FORMAT = "gentun-cnn-ensemble/1"
 OUTPUTS = ("proba", "label", "votes", "vote_label", "member_proba", "member_logits")
@@ -272,6 +273,38 @@ class CnnEnsemble(object):
         cam = cam_upsample(res[0], self.input_shape[:2]) if upsample else res[0]
         return (cam, {"target": res[1], "base": res[2]}) if return_info else cam
 
+    def saliency(self, x, target=None, score="logit", method="gradient", steps=16, baseline=0.0, reduce="absmax",
+                 device=None, batch=256, backend=None, return_info=False):
+        """Input-gradient saliency of the ensemble (``CnnClassifier.saliency``): the weighted mean, in member
+        order with :func:`combine_maps`' rounding, of the members' signed attributions ``a`` (before ``reduce``),
+        every member under its own score of the ensemble's target (``None``: the first maximum of the combined
+        probabilities). With ``score="proba"`` this is exactly the attribution of the combined probability (the
+        gradient is linear in the score); with ``"logit"`` it is that of the weighted mean of the members' logits.
+        ``info["base"]`` and ``info["baseline_score"]`` are the weighted means of the members' scores."""
+        steps, x0 = saliency_check(score, method, steps, baseline, reduce, batch, self.input_shape[2])
+        x = self.members[0]._check_x(x)
+        target = occlusion_targets(target, x.shape[0], self.classes, "saliency")
+        dev = torch.device("cpu" if device is None else device)
+        if backend is None:
+            backend = "hip" if dev.type == "cuda" else "torch"
+        if backend == "hip":
+            saliency_check_hip(self.classes, steps, method, 256)         # the class limit, before a predictor exists
+            pred = self.hip_predictor(dev, batch)
+            saliency_check_hip(self.classes, steps, method, pred.EB)
+            res = pred.saliency(x, target, score, method, steps, x0, reduce)
+        elif backend == "torch":
+            if target is None:
+                member = np.stack([m._torch_predict(x, dev, int(batch), torch.float32)[1] for m in self.members])
+                target = np.argmax(combine(member, self.weights)[0], axis=1).astype(np.int64)
+            per = [m._torch_saliency(x, target, score, method, steps, x0, dev, int(batch), torch.float32)
+                   for m in self.members]
+            res = (saliency_reduce(combine_maps([p[0] for p in per], self.weights), reduce), target,
+                   combine_maps([p[2] for p in per], self.weights),
+                   combine_maps([p[3] for p in per], self.weights) if method == "integrated" else None)
+        else:
+            raise ValueError("unknown backend {!r}".format(backend))
+        return (res[0], saliency_info(res, method)) if return_info else res[0]
+
     def predict_mc(self, x, samples=32, dropout=0.5, seed=0, device=None, batch=256, backend=None,
                    return_samples=False):
         """Monte-Carlo dropout of the ensemble (``CnnClassifier.predict_mc``): every member draws ``samples``
@@ -374,6 +407,7 @@ class HipEnsemblePredictor(object):
         self._cam = {}               # (score, relu) -> GradcamState, created on first use
         self._cam_wbar = None        # W1 summed over the real pixels (cam_wbar), on the first Grad-CAM request
         self._mc = None              # McState, created on the first Monte-Carlo dropout request
+        self._sal = None             # SaliencyState, created on the first saliency request
 
     def _host(self, ens, EB):
         from . import cnn_engine as E
@@ -426,6 +460,11 @@ class HipEnsemblePredictor(object):
         """``(map, target, base)`` of validated arguments (``CnnEnsemble.gradcam``) over the ``k`` members and
         their weights."""
         return gradcam_state(self, score, relu, self.k, self.weight).run(self, x, target)
+
+    def saliency(self, x, target, score, method, steps, x0, reduce):
+        """``(map, target, base, baseline_score)`` of validated arguments (``CnnEnsemble.saliency``) over the
+        ``k`` members and their weights."""
+        return saliency_state(self, self.k, self.weight).run(self, x, target, score, method, steps, x0, reduce)
 
     def predict_mc(self, x, samples, dropout, seed, return_samples):
         """The dict of validated arguments (``CnnEnsemble.predict_mc``) over the ``k`` members and their

@@ -22,6 +22,7 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
+from ..ops.cnn_kernels import IG_MAX_STEPS
 from .genome import ConvSpec, make_plan
 
 FORMAT = "gentun-cnn/1"
@@ -334,6 +335,80 @@ def cam_check_hip(plan, input_shape):
             hr, wr, CAM_MAX_PIXELS))
 
 
+SAL_METHODS = ("gradient", "gradxinput", "integrated")
+SAL_REDUCE = ("absmax", "sum", None)
+SAL_MAX_STEPS = IG_MAX_STEPS     # one constant: cnn_kernels checks it against the library's IG_MAXM
+
+
+def saliency_check(score, method, steps, baseline, reduce, batch, channels):
+    """The validated ``(steps, baseline fp32 [channels])`` of a saliency request; ``ValueError`` on a bad option,
+    before any work."""
+    if score not in CAM_SCORES:
+        raise ValueError("score {!r}: expected one of {}".format(score, CAM_SCORES))
+    if method not in SAL_METHODS:
+        raise ValueError("method {!r}: expected one of {}".format(method, SAL_METHODS))
+    if not (reduce is None or (isinstance(reduce, str) and reduce in SAL_REDUCE)):
+        raise ValueError("reduce {!r}: expected one of {}".format(reduce, SAL_REDUCE))
+    if not _is_int(steps) or not 1 <= int(steps) <= SAL_MAX_STEPS:
+        raise ValueError("saliency: steps must be an integer in [1, {}], got {!r}".format(SAL_MAX_STEPS, steps))
+    if not _is_int(batch) or int(batch) < 1:
+        raise ValueError("batch must be a positive integer")
+    try:
+        base = occlusion_fill(baseline, channels)
+    except ValueError:
+        raise ValueError("saliency: baseline must be a finite number or {} of them, got {!r}".format(
+            channels, baseline))
+    return int(steps), base
+
+
+def ig_alphas(steps):
+    """fp32 ``[steps]``: the midpoints ``(k + 0.5) / steps`` of integrated gradients, rounded once."""
+    return ((np.arange(steps, dtype=np.float64) + 0.5) / steps).astype(np.float32)
+
+
+def ig_point(x, x0, alpha):
+    """``x0 + alpha * (x - x0)`` in the dtype of ``x``, every operation rounded separately (``gt_ig_points``)."""
+    ft = x.dtype.type
+    return x0.astype(x.dtype) + ft(alpha) * (x - x0.astype(x.dtype))
+
+
+def saliency_finish(grads, x, x0, method):
+    """The signed attribution ``[n, H, W, C]`` of the gradients ``grads`` (a list: one array for ``"gradient"`` and
+    ``"gradxinput"``, one per interpolation point in ascending order for ``"integrated"``) in their dtype, as
+    ``gt_ig_reduce`` forms it: the ordered sum, ``* (1 / m)`` with ``1 / m`` rounded first, ``* (x - x0)``."""
+    ft = grads[0].dtype.type
+    acc = grads[0]
+    for g in grads[1:]:
+        acc = acc + g
+    if method == "gradient":
+        return acc
+    xs = x.astype(acc.dtype)
+    if method == "gradxinput":
+        return xs * acc
+    return (xs - x0.astype(acc.dtype)) * (acc * (ft(1) / ft(len(grads))))
+
+
+def saliency_reduce(a, reduce):
+    """The channel reduction of a signed attribution ``[n, H, W, C]``: ``"absmax"`` ``max_c |a|``, ``"sum"`` the
+    channels added in order, ``None`` the array itself."""
+    if reduce is None:
+        return a
+    if reduce == "absmax":
+        return np.abs(a).max(axis=3)
+    acc = a[..., 0]
+    for c in range(1, a.shape[3]):
+        acc = acc + a[..., c]
+    return acc
+
+
+def saliency_check_hip(classes, steps, method, EB):
+    """The ``ValueError`` of what the HIP saliency path does not take, before its state is built."""
+    if classes > 16:
+        raise ValueError("HIP head kernel supports at most 16 classes")
+    if method == "integrated" and steps > EB:
+        raise ValueError("saliency: {} steps do not fit {} rows per launch".format(steps, EB))
+
+
 def occlusion_by_views(scores, x, target, patch, stride, fill, batch, rows=4096):
     """The occlusion map by :func:`occlusion_views`: ``scores(images [k, H, W, C])`` returns ``(score, proba)``,
     fp32 ``[k, classes]`` each, ``batch`` rows per forward -- the score vectors to difference and the
@@ -590,6 +665,90 @@ class CnnClassifier(object):
             raise ValueError("unknown backend {!r}".format(backend))
         cam = cam_upsample(res[0], self.input_shape[:2]) if upsample else res[0]
         return (cam, {"target": res[1], "base": res[2]}) if return_info else cam
+
+    def saliency(self, x, target=None, score="logit", method="gradient", steps=16, baseline=0.0, reduce="absmax",
+                 device=None, batch=256, backend=None, return_info=False):
+        """Per-pixel attribution of ``x`` ``[n, H, W, C]`` (or one image) at input resolution, fp32. With ``s`` the
+        logit (``score="logit"``) or the probability (``"proba"``) of the target class (``None``: the model's own
+        label, one class index, or one per image -- :meth:`gradcam`'s definitions) and ``g = ds/dx``:
+
+        ``method="gradient"``: ``a = g(x)``; ``"gradxinput"``: ``a = x * g(x)``; ``"integrated"`` (Sundararajan et
+        al., midpoint rule): ``a = (x - x0) * (1/m) * sum_k g(x0 + ((k + 0.5)/m)(x - x0))`` with ``m = steps`` in
+        1..64 and ``x0 = baseline`` (a number or one per channel), the sum in ascending ``k`` in fp32
+        (:func:`saliency_finish`).
+
+        ``reduce="absmax"`` returns ``max_c |a|`` ``[n, H, W]``, ``"sum"`` the channels added in order, ``None`` the
+        signed ``[n, H, W, C]``. ``return_info=True`` returns ``(map, {"target": int64 [n], "base": fp32 [n]})``
+        with ``base = s(x)``; for ``"integrated"`` also ``"baseline_score"``, ``s(x0)`` per row, so that
+        ``a.sum() ~ base - baseline_score`` (completeness).
+
+        ``device`` / ``backend`` / ``batch`` as in :meth:`predict`: the CPU or ``backend="torch"`` runs the
+        stock-torch forward under autograd on the input; a ``cuda`` device runs the HIP predictor's forward with the
+        pool masks on, then the training step's own data-gradient launches in evaluation mode down to
+        ``gt_conv_in_dgrad`` (:class:`SaliencyState`)."""
+        steps, x0 = saliency_check(score, method, steps, baseline, reduce, batch, self.input_shape[2])
+        x = self._check_x(x)
+        target = occlusion_targets(target, x.shape[0], self.classes, "saliency")
+        dev = torch.device("cpu" if device is None else device)
+        if backend is None:
+            backend = "hip" if dev.type == "cuda" else "torch"
+        if backend == "hip":
+            saliency_check_hip(self.classes, steps, method, predict_batch(batch))
+            res = self.hip_predictor(dev, batch).saliency(x, target, score, method, steps, x0, reduce)
+        elif backend == "torch":
+            a, tgt, base, bs = self._torch_saliency(x, target, score, method, steps, x0, dev, int(batch),
+                                                    torch.float32)
+            res = (saliency_reduce(a, reduce), tgt, base, bs)
+        else:
+            raise ValueError("unknown backend {!r}".format(backend))
+        return (res[0], saliency_info(res, method)) if return_info else res[0]
+
+    def _torch_input_grad(self, x, target, score, dev, batch, dtype):
+        """``(g [n, H, W, C], target int64 [n], s [n])`` by stock torch in ``dtype``: the forward of
+        :meth:`_torch_predict` with autograd on the input, ``g = ds/dx`` for the score ``s`` of the target (the
+        first maximum of the probabilities where ``target`` is None). Chunks of ``batch`` rows, filled with zero
+        images to a multiple of 32 exactly as :meth:`_torch_predict` fills them. ``x`` may be fp64."""
+        P = self._tensors(dev, dtype)
+        n = x.shape[0]
+        h, w, c = self.input_shape
+        ftype = np.float64 if dtype == torch.float64 else np.float32
+        grad, base, tgt = np.empty((n, h, w, c), ftype), np.empty(n, ftype), np.empty(n, np.int64)
+        for s in range(0, n, batch):
+            m = min(batch, n - s)
+            buf = np.zeros(((m + 31) // 32 * 32, c, h, w), x.dtype)
+            buf[:m] = x[s:s + m].transpose(0, 3, 1, 2)
+            xb = torch.from_numpy(buf).to(device=dev, dtype=dtype).requires_grad_(True)
+            with torch.enable_grad():
+                logits = self._torch_forward(xb, P)
+                proba = torch.softmax(logits, dim=-1)
+                if target is None:                   # first maximum: the head kernels' scan
+                    t = np.argmax(proba[:m].detach().cpu().numpy(), axis=1).astype(np.int64)
+                else:
+                    t = target[s:s + m]
+                rows = torch.arange(m, device=dev)
+                picked = (logits if score == "logit" else proba)[rows, torch.from_numpy(t).to(dev)]
+                g, = torch.autograd.grad(picked.sum(), xb)
+            grad[s:s + m] = g[:m].permute(0, 2, 3, 1).cpu().numpy()
+            base[s:s + m] = picked.detach().cpu().numpy()
+            tgt[s:s + m] = t
+        return grad, tgt, base
+
+    def _torch_saliency(self, x, target, score, method, steps, x0, dev, batch, dtype):
+        """``(a [n, H, W, C] signed, target int64 [n], base [n], baseline_score [n] or None)`` by stock torch in
+        ``dtype`` (fp32, or fp64: the tests' reference, which also forms the interpolation points and the sums in
+        fp64): :meth:`_torch_input_grad` at ``x`` -- or, for ``"integrated"``, at every point of
+        :func:`ig_point` for the target and ``base`` of ``x`` itself -- finished by :func:`saliency_finish`."""
+        ftype = np.float64 if dtype == torch.float64 else np.float32
+        xs = x.astype(ftype)
+        g, tgt, base = self._torch_input_grad(xs, target, score, dev, batch, dtype)
+        if method != "integrated":
+            return saliency_finish([g], xs, x0, method), tgt, base, None
+        grads = [self._torch_input_grad(ig_point(xs, x0, al), tgt, score, dev, batch, dtype)[0]
+                 for al in ig_alphas(steps)]
+        zero = np.broadcast_to(x0, (1,) + self.input_shape).copy()
+        lg, pr = self._torch_predict(zero, dev, batch, dtype)
+        bs = (lg if score == "logit" else pr)[0][tgt]
+        return saliency_finish(grads, xs, x0, method), tgt, base, bs
 
     def predict_mc(self, x, samples=32, dropout=0.5, seed=0, device=None, batch=256, backend=None,
                    return_samples=False):
@@ -1184,6 +1343,244 @@ def mc_state(pred, G, weight):
     return pred._mc
 
 
+def saliency_info(res, method):
+    """The ``return_info`` dict of ``(map, target, base, baseline_score)``."""
+    info = {"target": res[1], "base": res[2]}
+    if method == "integrated":
+        info["baseline_score"] = res[3]
+    return info
+
+
+class SaliencyState(object):
+    """What a HIP predictor (``HipPredictor`` or ``HipEnsemblePredictor``) adds for input-gradient saliency: an
+    evaluation-mode backward chain over the predictor's own activations, down to the staging tensor.
+
+    * the masked forward: copies of the predictor's evaluation launches with the pool argmax masks switched back
+      on (``pmask`` twins at ``EB`` rows, in the fused conv / BN-apply epilogues and the separate pool launch);
+      the activations are the plain forward's, byte for byte;
+    * ``gt_head_saliency``: label, base score and ``dH`` of every member;
+    * the job's own backward records (``bwd_ops``) without the weight gradients: ``gt_dense_dgrad`` and every
+      data-gradient / pool-backward launch copied with its pointers remapped to gradient twins at ``EB`` rows,
+      the fused un-pools kept, ``gt_bn_bwd_eval`` in place of each BatchNorm backward;
+    * ``gt_conv_in_dgrad``, the data gradient of the input conv, then ``gt_ig_reduce``.
+
+    One stream, no graph. The gradient twins and masks double the predictor's twin footprint. The predictor's
+    job, evaluation launches, staging tensor and ``upload`` are used as they are."""
+
+    def __init__(self, pred, G, weight):
+        K, job, EB, dev = pred.K, pred.job, pred.EB, pred.device
+        Q = job.Q
+        self.G, self.weight = G, weight
+        rows, remap = job._eval_remap                # the activation twins of the predictor's own evaluation launches
+        remap = dict(remap)
+        must = [t.data_ptr() for t in list(job.act.values()) + list(job.zpre.values()) + [job.hdrop]]
+        if rows != EB or any(p not in remap for p in must):
+            raise RuntimeError("saliency: the predictor's evaluation launches have no twin of some activation")
+        self.grad = {}
+        for name, t in job.grad.items():
+            e = self.grad[name] = torch.zeros((Q, EB) + tuple(t.shape[2:]), dtype=t.dtype, device=dev)
+            remap[t.data_ptr()] = e.data_ptr()
+        self.pmask = []
+        for st in job.stages:
+            e = torch.zeros((Q * EB,) + tuple(st.pmask.shape[1:]), dtype=torch.uint8, device=dev)
+            self.pmask.append(e)
+            remap[st.pmask.data_ptr()] = e.data_ptr()
+
+        small = set(t.data_ptr() for t in list(job.grad.values()) + [st.pmask for st in job.stages]) | set(must)
+
+        def rp(ptr):
+            """A training-batch buffer -> its twin at ``EB`` rows (a missing twin is an error, never a launch over
+            the short buffer); the dataset, parameters and tables stay."""
+            ptr = ptr or 0
+            if ptr in small and ptr not in remap:
+                raise RuntimeError("saliency: no twin at {} rows for the buffer at {:#x}".format(EB, ptr))
+            return remap.get(ptr, ptr)
+        # ---- masked forward
+        self.fwd_ops = []
+        for (kind, a, mk), (_, b, _) in zip(job.fwd_ops, pred.ops):
+            if kind == "conv":
+                c = K.ConvArgs.from_buffer_copy(b)
+                c.pool_mask = rp(a.pool_mask)
+                self.fwd_ops.append((kind, c, None))
+            elif kind == "bn":
+                c = K.BnArgs.from_buffer_copy(b)
+                c.pool_mask = rp(a.pool_mask)
+                self.fwd_ops.append((kind, c, None))
+            else:
+                self.fwd_ops.append((kind, b, rp(mk)))
+        # ---- head and dense data gradient
+        self.tgt = torch.full((EB,), -1, dtype=torch.int32, device=dev)
+        self.base = torch.empty(EB, dtype=torch.float32, device=dev)
+        self.dH = torch.zeros((Q, EB, job.Up), dtype=torch.float32, device=dev)
+        self.dHp = torch.zeros((job.npl, Q, EB, job.Up), dtype=torch.int16, device=dev)
+        h = K.HeadSaliencyArgs()
+        h.plog, h.b2, h.weight = pred.df.plog, job.views["b2"][0].data_ptr(), weight.data_ptr()
+        h.hid, h.w2 = pred.df.out, pred.df.w2
+        h.tgt, h.base, h.dH, h.dHp = (self.tgt.data_ptr(), self.base.data_ptr(), self.dH.data_ptr(),
+                                      self.dHp.data_ptr())
+        h.G, h.B, h.Up, h.C, h.prec = G, EB, job.Up, pred.classes, pred.df.prec
+        self.head = h
+        dd = K.DenseDgradArgs.from_buffer_copy(job.dense_dgrad_args)
+        dd.dH, dd.dHp, dd.dx, dd.B = self.dH.data_ptr(), self.dHp.data_ptr(), rp(dd.dx), EB
+        dd.unpool_mask, dd.unpool_x0, dd.unpool_x1 = rp(dd.unpool_mask), rp(dd.unpool_x0), rp(dd.unpool_x1)
+        self.dd = dd
+        # ---- the backward chain
+        self.bwd = []
+        for kind, a, L in job.bwd_ops:
+            if kind == "conv":
+                c = K.ConvArgs.from_buffer_copy(a)
+                for i in range(K.MAXSLOT):
+                    c.inp[i], c.out[i], c.out_mask[i] = rp(c.inp[i]), rp(c.out[i]), rp(c.out_mask[i])
+                c.pool_y, c.pool_mask, c.unpool_x1 = rp(c.pool_y), rp(c.pool_mask), rp(c.unpool_x1)
+                c.st, c.B = job.eval_state.data_ptr(), EB
+                job._set_twopass(c)
+                if L.slots[0] in job.unpool_fused and not job.L.gt_conv_fast_probe_any(c):
+                    raise RuntimeError("saliency: no kernel un-pools the gradient of {} at {} rows".format(
+                        L.slots[0], EB))
+                self.bwd.append(("conv", c))
+            elif kind == "pool_bwd":
+                pm, sel, gp, g0, g1, _qb, _b, hh, ww, cc, one, prec = a
+                self.bwd.append(("pool_bwd", (rp(pm), sel, rp(gp), rp(g0), rp(g1), Q * EB, EB, hh, ww, cc, one, prec)))
+            elif kind == "bn_bwd":
+                b = K.BnBwdEvalArgs()
+                b.dy, b.gamma, b.run = self.grad[L.name].data_ptr(), L.gamma[0].data_ptr(), L.bn_run.data_ptr()
+                b.G, b.B, b.H, b.W, b.Cp, b.Cr = Q, EB, L.H, L.W, L.coutp, L.cout
+                b.Hr, b.Wr = (L.Hr, L.Wr) if job.pad_hw is not None else (L.H, L.W)
+                b.chunk_px = L.bn_chunk
+                b.nchunk = -(-(EB * L.H * L.W) // L.bn_chunk)
+                b.eps, b.prec = job.cfg.bn_eps, job.prec
+                self.bwd.append(("bn_bwd", b))
+        # ---- the input conv's data gradient and the finishing kernel
+        L0 = job.stages[0].layers[0]
+        stage = pred.stage
+        self.dx = torch.zeros((Q, EB) + tuple(stage.shape[1:]), dtype=torch.float32, device=dev)
+        ci = K.ConvInDgradArgs()
+        ci.dz, ci.w, ci.dx = self.grad[L0.name].data_ptr(), L0.w[0].data_ptr(), self.dx.data_ptr()
+        ci.G, ci.B, ci.Hp, ci.Wp = Q, EB, L0.H, L0.W
+        ci.Hr, ci.Wr = pred.hwc[0], pred.hwc[1]
+        ci.Coutp, ci.Cout, ci.C8, ci.Cr, ci.KH, ci.KW, ci.prec = L0.coutp, L0.cout, L0.cinp, L0.cin, L0.KH, L0.KW, job.prec
+        self.cin = ci
+        h_, w_, c_ = pred.hwc
+        self.raw = torch.zeros_like(stage)                       # the images of an integrated-gradients chunk
+        self.x0 = torch.zeros(int(stage.shape[3]), dtype=torch.float32, device=dev)
+        self.out = torch.empty(EB * h_ * w_ * c_, dtype=torch.float32, device=dev)
+        r = K.IgReduceArgs()
+        r.dx, r.x0, r.weight, r.out = self.dx.data_ptr(), self.x0.data_ptr(), weight.data_ptr(), self.out.data_ptr()
+        r.G, r.B = G, EB
+        r.Hp, r.Wp, r.Hr, r.Wr, r.Cr = int(stage.shape[1]), int(stage.shape[2]), h_, w_, c_
+        r.prec = 1 if stage.dtype == torch.float32 else 0
+        self.red = r
+        p = K.IgPointsArgs()
+        p.raw, p.out, p.x0, p.rows = self.raw.data_ptr(), stage.data_ptr(), self.x0.data_ptr(), EB
+        p.Hp, p.Wp, p.Hr, p.Wr, p.Cr, p.prec = r.Hp, r.Wp, h_, w_, c_, r.prec
+        self.pts = p
+
+    def forward(self, pred, rows, logit):
+        """Masked forward and head of the staging tensor on the current stream: ``tgt`` / ``base`` / ``dH`` of the
+        first ``rows`` rows."""
+        job, K = pred.job, pred.K
+        s = job._stream()
+        self.head.m, self.head.logit = rows, logit
+        job._run_fwd(s, self.fwd_ops)
+        K.check(job.L.gt_dense_fwd(pred.df, s), "dense_fwd(saliency)")
+        K.check(job.L.gt_head_saliency(self.head, s), "head_saliency")
+
+    def backward(self, pred, rows):
+        """``dH`` -> ``dx`` of the first ``rows`` rows: the dense data gradient, the remapped chain and the input
+        conv's data gradient, on the current stream."""
+        job, K = pred.job, pred.K
+        L, s = job.L, job._stream()
+        K.check(L.gt_dense_dgrad(self.dd, s), "dense_dgrad(saliency)")
+        for kind, a in self.bwd:
+            if kind == "conv":
+                K.check(L.gt_conv_fwd(a, s), "conv_dgrad(saliency)")
+            elif kind == "bn_bwd":
+                K.check(L.gt_bn_bwd_eval(a, s), "bn_bwd_eval")
+            else:
+                K.check(L.gt_pool_bwd_mask(*a, s), "pool_bwd(saliency)")
+        self.cin.m = rows
+        K.check(L.gt_conv_in_dgrad(self.cin, s), "conv_in_dgrad")
+
+    def reduce(self, pred, x, R, m, method, reduce):
+        """``gt_ig_reduce`` of ``R`` raw rows whose images are the first rows of ``x``."""
+        r = self.red
+        r.x, r.R, r.m = x.data_ptr(), R, m
+        r.method, r.reduce = SAL_METHODS.index(method), {None: 0, "absmax": 1, "sum": 2}[reduce]
+        r.inv_m = float(np.float32(1) / np.float32(m))
+        pred.K.check(pred.job.L.gt_ig_reduce(r, pred.job._stream()), "ig_reduce")
+
+    def _set_targets(self, target, s, m):
+        if target is None:
+            self.tgt.fill_(-1)                   # the kernel puts the label there
+        else:
+            self.tgt[:m].copy_(torch.from_numpy(target[s:s + m].astype(np.int32)).to(self.tgt.device))
+
+    def run(self, pred, x, target, score, method, steps, x0, reduce):
+        """``x`` [n, H, W, C] host fp32 -> ``(map, target int64 [n], base fp32 [n], baseline_score or None)`` as
+        host arrays. ``"gradient"`` / ``"gradxinput"``: per chunk of ``EB`` images one upload and one launch set.
+        ``"integrated"``: per chunk of ``R = EB // steps`` images one upload, a forward of the images themselves
+        (label and base score), ``gt_ig_points`` and one launch set over the ``steps * R`` points; one more
+        forward per call scores the baseline. Results gather on the device and are read back once."""
+        n, EB, dev = x.shape[0], pred.EB, pred.device
+        h, w, c = pred.hwc
+        logit = 1 if score == "logit" else 0
+        per = h * w * (c if reduce is None else 1)
+        ig = method == "integrated"
+        m = steps if ig else 1
+        R = EB // m if ig else EB
+        with torch.cuda.device(dev):
+            out = torch.empty(n * per, dtype=torch.float32, device=dev)
+            tgt = torch.empty(n, dtype=torch.int32, device=dev)
+            base = torch.empty(n, dtype=torch.float32, device=dev)
+            bscore = None
+            self.x0.zero_()
+            if ig:
+                f = torch.zeros(int(pred.stage.shape[3]), dtype=torch.float32)
+                f[:c] = torch.from_numpy(x0)
+                self.x0.copy_(f.to(pred.stage.dtype).float().to(dev))    # rounded to the staging type on the host
+                C = pred.classes                                         # s(x0) of every class: row k, target k
+                pred.upload(np.broadcast_to(self.x0[:c].cpu().numpy(), (C, h, w, c)).copy())
+                self.tgt[:C].copy_(torch.arange(C, dtype=torch.int32, device=dev))
+                self.forward(pred, C, logit)
+                bscore = self.base[:C].clone()
+                self.pts.m = m
+                for k, al in enumerate(ig_alphas(m)):
+                    self.pts.alpha[k] = float(al)
+            for s in range(0, n, R):
+                mm = min(R, n - s)
+                pred.upload(x[s:s + mm])
+                self._set_targets(target, s, mm)
+                rows = mm
+                if ig:                                                   # a short last chunk runs m * mm points only
+                    self.forward(pred, mm, logit)                        # label and base score of the images
+                    tgt[s:s + mm].copy_(self.tgt[:mm])
+                    base[s:s + mm].copy_(self.base[:mm])
+                    self.raw[:mm].copy_(pred.stage[:mm])
+                    self.tgt[:m * mm].copy_(self.tgt[:mm].repeat(m))     # row k * mm + r: the target of image r
+                    self.pts.R = mm
+                    pred.K.check(pred.job.L.gt_ig_points(self.pts, pred.job._stream()), "ig_points")
+                    rows = m * mm
+                self.forward(pred, rows, logit)
+                self.backward(pred, rows)
+                self.reduce(pred, self.raw if ig else pred.stage, mm, m, method, reduce)
+                out[s * per:(s + mm) * per].copy_(self.out[:mm * per])
+                if not ig:
+                    tgt[s:s + mm].copy_(self.tgt[:mm])
+                    base[s:s + mm].copy_(self.base[:mm])
+            t = tgt.cpu().numpy().astype(np.int64)
+            shape = (n, h, w, c) if reduce is None else (n, h, w)
+            return (out.cpu().numpy().reshape(shape), t, base.cpu().numpy(),
+                    None if bscore is None else bscore.cpu().numpy()[t])
+
+
+def saliency_state(pred, G, weight):
+    """The cached :class:`SaliencyState` of a predictor (its ``_sal``), built on the first request."""
+    if pred._sal is None:
+        with torch.cuda.device(pred.device):
+            pred._sal = SaliencyState(pred, G, weight)
+    return pred._sal
+
+
 class HipPredictor(object):
     """Forward-only HIP launches of one fitted model at ``EB`` rows per launch.
 
@@ -1236,6 +1633,7 @@ class HipPredictor(object):
         self._cam = {}               # (score, relu) -> GradcamState, created on first use
         self._cam_wbar = None        # W1 summed over the real pixels (cam_wbar), on the first Grad-CAM request
         self._mc = None              # McState, created on the first Monte-Carlo dropout request
+        self._sal = None             # SaliencyState, created on the first saliency request
 
     def forward(self):
         """The launches of one chunk on the current stream: staging tensor -> ``logits`` / ``proba``."""
@@ -1281,6 +1679,13 @@ class HipPredictor(object):
         if self._one is None:
             self._one = torch.ones(1, dtype=torch.float32, device=self.device)
         return mc_state(self, 1, self._one).run(self, x, samples, dropout, seed, return_samples)
+
+    def saliency(self, x, target, score, method, steps, x0, reduce):
+        """``(map, target, base, baseline_score)`` of validated arguments (``CnnClassifier.saliency``): one member
+        of weight 1.0 (``1.0f * v`` is ``v``)."""
+        if self._one is None:
+            self._one = torch.ones(1, dtype=torch.float32, device=self.device)
+        return saliency_state(self, 1, self._one).run(self, x, target, score, method, steps, x0, reduce)
 
     def run(self, x, views=None):
         """``x`` [n, H, W, C] host fp32 -> (logits, proba) host fp32 ``[n, classes]``; with ``views`` (a tuple

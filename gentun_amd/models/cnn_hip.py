@@ -1148,6 +1148,7 @@ class HipPopJob(FoldJob):
         hd = K.HeadArgs.from_buffer_copy(self.head_args)
         hd.h, hd.plog = hdrop.data_ptr(), plog.data_ptr()
         hd.B, hd.eval, hd.st = EB, 1, self.eval_state.data_ptr()
+        self._eval_remap = (EB, dict(remap))     # training buffer -> its twin, for whoever adds launches over the twins
         return ops, df, hd, keep
 
     def evaluate(self):

@@ -226,6 +226,44 @@ class HeadMcArgs(C.Structure):
                 ("keep_scale", C.c_float), ("inv_T", C.c_float)]
 
 
+class HeadSaliencyArgs(C.Structure):
+    """csrc/hip/cnn_dense.hip HeadSaliencyArgs: target, base score and the hidden gradient ``dH`` (with its bf16
+    planes) of every member, the seed of the evaluation-mode backward chain (gt_head_saliency)."""
+    _fields_ = [("plog", P), ("b2", P), ("weight", P), ("hid", P), ("w2", P), ("tgt", P), ("base", P), ("dH", P),
+                ("dHp", P), ("G", I), ("B", I), ("Up", I), ("C", I), ("m", I), ("prec", I), ("logit", I)]
+
+
+class ConvInDgradArgs(C.Structure):
+    """csrc/hip/cnn_saliency.hip ConvInDgradArgs: the data gradient of the network's input conv
+    (gt_conv_in_dgrad)."""
+    _fields_ = [("dz", P), ("w", P), ("dx", P), ("G", I), ("B", I), ("m", I), ("Hp", I), ("Wp", I), ("Hr", I),
+                ("Wr", I), ("Coutp", I), ("Cout", I), ("C8", I), ("Cr", I), ("KH", I), ("KW", I), ("prec", I)]
+
+
+class BnBwdEvalArgs(C.Structure):
+    """csrc/hip/cnn_saliency.hip BnBwdEvalArgs: BatchNorm backward under running statistics (gt_bn_bwd_eval)."""
+    _fields_ = [("dy", P), ("gamma", P), ("run", P), ("G", I), ("B", I), ("H", I), ("W", I), ("Hr", I), ("Wr", I),
+                ("Cp", I), ("Cr", I), ("nchunk", I), ("chunk_px", I), ("eps", C.c_float), ("prec", I)]
+
+
+IG_MAX_STEPS = 64       # points of one integrated-gradients path at most (csrc/hip/cnn_saliency.hip IG_MAXM)
+
+
+class IgPointsArgs(C.Structure):
+    """csrc/hip/cnn_saliency.hip IgPointsArgs: the interpolation points of a raw chunk into the staging tensor
+    (gt_ig_points)."""
+    _fields_ = [("raw", P), ("out", P), ("x0", P), ("R", I), ("m", I), ("rows", I), ("Hp", I), ("Wp", I),
+                ("Hr", I), ("Wr", I), ("Cr", I), ("prec", I), ("alpha", C.c_float * IG_MAX_STEPS)]
+
+
+class IgReduceArgs(C.Structure):
+    """csrc/hip/cnn_saliency.hip IgReduceArgs: input gradients -> the attribution map of every raw row
+    (gt_ig_reduce)."""
+    _fields_ = [("dx", P), ("x", P), ("x0", P), ("weight", P), ("out", P), ("G", I), ("B", I), ("R", I), ("m", I),
+                ("Hp", I), ("Wp", I), ("Hr", I), ("Wr", I), ("Cr", I), ("method", I), ("reduce", I), ("prec", I),
+                ("inv_m", C.c_float)]
+
+
 MC_MAX_SAMPLES = 64     # samples of one Monte-Carlo dropout request at most (csrc/hip/cnn_head_mc.hip MC_MAXT)
 
 
@@ -393,6 +431,18 @@ def lib():
         L.gt_head_mc.restype = I
         L.gt_sizeof_head_mc_args.restype = C.c_size_t
         assert L.gt_sizeof_head_mc_args() == C.sizeof(HeadMcArgs), "HeadMcArgs ABI mismatch"
+        for fname, sname, st in (("gt_head_saliency", "head_saliency", HeadSaliencyArgs),
+                                 ("gt_conv_in_dgrad", "conv_in_dgrad", ConvInDgradArgs),
+                                 ("gt_bn_bwd_eval", "bn_bwd_eval", BnBwdEvalArgs),
+                                 ("gt_ig_points", "ig_points", IgPointsArgs),
+                                 ("gt_ig_reduce", "ig_reduce", IgReduceArgs)):
+            fn = getattr(L, fname)
+            fn.argtypes = [C.POINTER(st), P]
+            fn.restype = I
+            size = getattr(L, "gt_sizeof_{}_args".format(sname))
+            size.restype = C.c_size_t
+            assert size() == C.sizeof(st), st.__name__ + " ABI mismatch"
+        assert L.gt_ig_max_steps() == IG_MAX_STEPS, "IG_MAX_STEPS mismatch"
         L.gt_occlude_views.argtypes = [C.POINTER(OccludeArgs), P]
         L.gt_occlude_views.restype = I
         L.gt_sizeof_occlude_args.restype = C.c_size_t

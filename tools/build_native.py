@@ -55,6 +55,7 @@ TARGETS = {
 # and ignores it)
 HIP_EXTRA_FLAGS = {
     "cnn_head_mc.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+    "cnn_saliency.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
 }
 
 

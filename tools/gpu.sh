@@ -22,7 +22,8 @@
 #   bash tools/gpu.sh cnn-tta                 predict(tta=...): views and mean on the device vs V plain HIP predicts combined in numpy vs stock torch, classifier and k-ensemble (ROWS= FIT_ROWS= K= REPS= OUT=)
 #   bash tools/gpu.sh cnn-occlusion           occlusion(): copies built and packed on the device vs occlusion_views in numpy + plain HIP predicts vs stock torch, classifier and k-ensemble (ROWS= FIT_ROWS= K= REPS= OUT= TIME=)
 #   bash tools/gpu.sh cnn-gradcam             gradcam(): forward + gt_head_gradcam vs plain HIP predict (the floor) vs stock-torch autograd vs occlusion(patch=4), classifier and k-ensemble; the new kernels' device time by events and by a kernel trace run of its own (ROWS= OCC_ROWS= FIT_ROWS= K= REPS= OUT= TIME=)
-#   bash tools/gpu.sh cnn-mc                  predict_mc(): forward + gt_head_mc vs plain HIP predict (the floor) vs the stock-torch backend, classifier and k-ensemble; the kernel's device time by a kernel trace run of its own (ROWS= SAMPLES= FIT_ROWS= K= REPS= OUT= TIME=)
+#   bash tools/gpu.sh cnn-saliency            saliency(): masked forward + backward chain + gt_conv_in_dgrad vs plain HIP predict (the floor) vs the stock-torch backend, integrated gradients on IG_ROWS rows, classifier and k-ensemble; the kernels' device time by a kernel trace run of its own (ROWS= IG_ROWS= STEPS= FIT_ROWS= K= REPS= OUT= TIME=)
+#   bash tools/gpu.sh cnn-mc                predict_mc(): forward + gt_head_mc vs plain HIP predict (the floor) vs the stock-torch backend, classifier and k-ensemble; the kernel's device time by a kernel trace run of its own (ROWS= SAMPLES= FIT_ROWS= K= REPS= OUT= TIME=)
 #   bash tools/gpu.sh rehearse                2-rank torchrun bench on one GPU (gloo control plane)
 #   bash tools/gpu.sh secondary               bench lines: reference fold semantics, torch comparator
 #
@@ -245,6 +246,21 @@ cnn-mc)
     --k ${K:-4} ${MC_ARGS:-} > $out/prof.log 2>&1 &&
   find /tmp/prof_mc -name "*kernel_stats.csv" -exec cp {} $out/kernel_stats.csv \; &&
   grep -E "Name|head_mc|head_predict|head_ensemble|dense_fwd" $out/kernel_stats.csv | cut -c1-300; rc=$?
+  [ $rc -eq 0 ] || { tail -5 $out/bench.err $out/prof.log 2>/dev/null; cut -c1-2000 $out/bench.json; }
+  exit $rc ;;
+cnn-saliency)
+  # the result line, then the backward chain's own durations from a kernel trace of one child run of its own (fits,
+  # then three saliency calls per model); the files are kept under $OUT
+  out=${OUT:-/tmp/cnn_saliency}; heartbeat; mkdir -p $out; rocprof_env; rm -rf /tmp/prof_sal
+  timeout -k 10 ${TIME:-600} python -u tools/bench_cnn_saliency.py --rows ${ROWS:-10000} --ig-rows ${IG_ROWS:-1000} \
+    --steps ${STEPS:-16} --fit-rows ${FIT_ROWS:-2000} --k ${K:-4} --reps ${REPS:-5} ${SAL_ARGS:-} \
+    > $out/bench.json 2> $out/bench.err &&
+  tail -1 $out/bench.json | cut -c1-8000 &&
+  timeout -k 10 300 rocprofv3 --kernel-trace --stats -d /tmp/prof_sal -o run --output-format csv -- \
+    python3 tools/bench_cnn_saliency.py --trace --rows ${ROWS:-10000} --fit-rows ${FIT_ROWS:-2000} --k ${K:-4} \
+    ${SAL_ARGS:-} > $out/prof.log 2>&1 &&
+  find /tmp/prof_sal -name "*kernel_stats.csv" -exec cp {} $out/kernel_stats.csv \; &&
+  grep -E "Name|conv_in_dgrad|head_saliency|ig_reduce|dense_dgrad|conv_fast|head_predict" $out/kernel_stats.csv | cut -c1-300; rc=$?
   [ $rc -eq 0 ] || { tail -5 $out/bench.err $out/prof.log 2>/dev/null; cut -c1-2000 $out/bench.json; }
   exit $rc ;;
 rehearse)
