@@ -777,6 +777,47 @@ __global__ void __launch_bounds__(256) head_occlusion_kernel(HeadOcclusionArgs a
   }
 }
 
+// RISE head (models/cnn_fitted.py, models/cnn_ensemble.py): the launch's rows are masked copies of a group of m
+// raw images, row j the item w = w0 + j = r * masks + i (gt_rise_views, cnn_rise.hip). A row's score vector is
+// formed exactly as head_occlusion_kernel forms it; the raw score of the image's target goes to S[r * Kp + i],
+// the operand of gt_rise_accumulate. Entries [masks, Kp) of a row of S are left alone.
+struct HeadRiseArgs {
+  const float* plog;       // [G][Up/16][B][C] partial logits from dense_fwd (evaluation mode)
+  const float* b2;         // [G][C]
+  const float* weight;     // [G] fp32, normalised on the host
+  const int* tgt;          // [m] target class per image, in [0, C) (gt_head_occlusion phase 0 resolves it)
+  float* S;                // [m][Kp]
+  int G, B, Up, C;         // B: the launch's rows (plog's stride)
+  int m, masks, Kp, w0;
+  int logit;
+};
+
+// head_occlusion_kernel's phase 1 with another last line: one workgroup of 4 waves per launch row, wave w runs
+// head_row_softmax for members w, w + 4, ..., wave 0 combines them in member order by ensemble_mean.
+__global__ void __launch_bounds__(256) head_rise_kernel(HeadRiseArgs a) {
+  __shared__ float ps[ENS_MAXG][HEAD_MAXC];
+  __shared__ float ls[HEAD_MAXC];                  // the one member's logits (logit mode)
+  const int b = blockIdx.x, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int C = a.C, nt = a.Up / 16;
+  const long w = (long)a.w0 + b;
+  if (w >= (long)a.m * a.masks) return;            // block-uniform: no barrier is skipped
+  for (int g = wave; g < a.G; g += 4) {
+    float lo, pr;
+    head_row_softmax(a.plog + ((long)g * nt * a.B + b) * C, a.b2 + (long)g * C, a.B, C, nt, lane, lo, pr);
+    if (lane < C) {
+      ps[g][lane] = pr;
+      if (a.logit) ls[lane] = lo;
+    }
+  }
+  __syncthreads();
+  if (wave != 0) return;
+  const float mean = lane < C ? ensemble_mean(a.weight, ps, a.G, lane) : 0.f;
+  const float score = a.logit ? (lane < C ? ls[lane] : 0.f) : mean;
+  const long r = w / a.masks;
+  const float s = __shfl(score, a.tgt[r]);
+  if (lane == 0) a.S[r * a.Kp + (w - r * a.masks)] = s;
+}
+
 // Grad-CAM (models/cnn_fitted.py, models/cnn_ensemble.py) at the network's last feature map A[c][i][j], the
 // pooled map dense_fwd reads as [hs][ws][Cp] features. The score's gradient passes through the dense head only,
 // and the channel weight alpha[c] = mean_{i,j} dS/dA[c][i][j] = (1 / (hr * wr)) * sum_u dH[u] * wbar[c][u] needs
@@ -1695,6 +1736,22 @@ int gt_head_occlusion(const HeadOcclusionArgs* a, hipStream_t stream) {
   return (int)hipGetLastError();
 }
 
+// One workgroup per item of [w0, min(w0 + B, m * masks)).
+int gt_head_rise(const HeadRiseArgs* a, hipStream_t stream) {
+  if (!a) return -3;
+  if (a->C < 1 || a->C > HEAD_MAXC || a->G < 1 || a->G > ENS_MAXG || a->B < 1) return -1;
+  if (a->Up < 16 || a->Up % 16) return -2;
+  if (!a->plog || !a->b2 || !a->weight || !a->tgt || !a->S) return -3;
+  if (a->masks < 1 || a->masks > 8192 || a->Kp != (a->masks + 31) / 32 * 32) return -4;
+  if (a->m < 1 || (long)a->m * a->masks > 0x7fffffffL) return -4;
+  if (a->logit != 0 && a->logit != 1) return -4;
+  if (a->logit && a->G != 1) return -5;
+  if (a->w0 < 0 || a->w0 >= (long)a->m * a->masks) return -4;
+  const long blocks = std::min((long)a->B, (long)a->m * a->masks - a->w0);
+  hipLaunchKernelGGL(head_rise_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, *a);
+  return (int)hipGetLastError();
+}
+
 static bool cam_geometry_ok(int G, int hs, int ws, int hr, int wr, int Cp, int Cr, int Up) {
   if (G < 1 || G > ENS_MAXG) return false;
   if (Up < 16 || Up % 16 || Up > CAM_MAXU) return false;
@@ -1789,6 +1846,7 @@ size_t gt_sizeof_head_predict_args() { return sizeof(HeadPredictArgs); }
 size_t gt_sizeof_head_ensemble_args() { return sizeof(HeadEnsembleArgs); }
 size_t gt_sizeof_head_tta_args() { return sizeof(HeadTtaArgs); }
 size_t gt_sizeof_head_occlusion_args() { return sizeof(HeadOcclusionArgs); }
+size_t gt_sizeof_head_rise_args() { return sizeof(HeadRiseArgs); }
 size_t gt_sizeof_cam_w1sum_args() { return sizeof(CamW1SumArgs); }
 size_t gt_sizeof_head_gradcam_args() { return sizeof(HeadGradcamArgs); }
 size_t gt_sizeof_head_saliency_args() { return sizeof(HeadSaliencyArgs); }

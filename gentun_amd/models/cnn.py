@@ -214,6 +214,13 @@ class GeneticCnnModel(GentunModel):
         kwargs.setdefault("device", self.device)
         return self.fitted.occlusion(x, **kwargs)
 
+    def rise(self, x, **kwargs):
+        """``self.fitted.rise`` on this model's device unless ``device`` says otherwise."""
+        if self.fitted is None:
+            raise RuntimeError("GeneticCnnModel.rise before fit()")
+        kwargs.setdefault("device", self.device)
+        return self.fitted.rise(x, **kwargs)
+
     def gradcam(self, x, **kwargs):
         """``self.fitted.gradcam`` on this model's device unless ``device`` says otherwise."""
         if self.fitted is None:

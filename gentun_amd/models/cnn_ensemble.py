@@ -26,7 +26,8 @@ import torch
 
 from .cnn_fitted import (CnnClassifier, TtaState, cam_check, cam_check_hip, cam_upsample, gradcam_state, mc_check,
                          mc_check_hip, mc_result, mc_state, mc_statistics, occlusion_by_views, occlusion_fill,
-                         occlusion_grid, occlusion_state, occlusion_targets, predict_batch, saliency_check,
+                         occlusion_grid, occlusion_state, occlusion_targets, predict_batch, rise_by_views,
+                         rise_check, rise_check_hip, rise_state, saliency_check,
                          saliency_check_hip, saliency_info, saliency_reduce, saliency_state, tta_views)
 
 FORMAT = "gentun-cnn-ensemble/1"
@@ -238,6 +239,34 @@ class CnnEnsemble(object):
             raise ValueError("unknown backend {!r}".format(backend))
         return (res[0], {"target": res[1], "base": res[2]}) if return_info else res[0]
 
+    def rise(self, x, target=None, masks=2048, cells=7, p=0.5, seed=0, fill=0.0, score="proba", device=None,
+             batch=256, backend=None, return_info=False):
+        """RISE saliency of the ensemble, ``CnnClassifier.rise`` with the weighted mean of the members'
+        probabilities (``"proba"`` of :meth:`predict`) as the score: fp32 ``[n, H, W]``. ``target=None``: the
+        first maximum of the weighted mean of the unmasked image. The members' logits have no weighted mean
+        here: ``score="logit"`` raises ``ValueError``."""
+        if score != "proba":
+            raise ValueError("score {!r}: an ensemble's rise score is 'proba'".format(score))
+        x = self.members[0]._check_x(x)
+        masks, cells, p, seed = rise_check(self.input_shape, x.shape[0], masks, cells, p, seed, batch)
+        fill = occlusion_fill(fill, self.input_shape[2])
+        target = occlusion_targets(target, x.shape[0], self.classes, "rise")
+        dev = torch.device("cpu" if device is None else device)
+        if backend is None:
+            backend = "hip" if dev.type == "cuda" else "torch"
+        if backend == "hip":
+            rise_check_hip(self.classes)
+            res = self.hip_predictor(dev, batch).rise(x, target, masks, cells, p, seed, fill)
+        elif backend == "torch":
+            def scores(images):
+                member = np.stack([m._torch_predict(images, dev, int(batch), torch.float32)[1] for m in self.members])
+                proba = combine(member, self.weights)[0]
+                return proba, proba
+            res = rise_by_views(scores, x, target, masks, cells, p, seed, fill, int(batch))
+        else:
+            raise ValueError("unknown backend {!r}".format(backend))
+        return (res[0], {"target": res[1], "base": res[2]}) if return_info else res[0]
+
     def gradcam(self, x, target=None, score="logit", relu=True, upsample=False, device=None, batch=256,
                 backend=None, return_info=False):
         """Grad-CAM of the ensemble (``CnnClassifier.gradcam``): fp32 ``[n, hr, wr]``, the weighted mean, in member
@@ -404,6 +433,7 @@ class HipEnsemblePredictor(object):
                 self.heads[members] = a
         self._tta = {}               # views -> TtaState, created on first use
         self._occ = {}               # (patch, stride, fill, score) -> OcclusionState, created on first use
+        self._rise = {}              # (masks, cells, p, seed, fill, score) -> RiseState, created on first use
         self._cam = {}               # (score, relu) -> GradcamState, created on first use
         self._cam_wbar = None        # W1 summed over the real pixels (cam_wbar), on the first Grad-CAM request
         self._mc = None              # McState, created on the first Monte-Carlo dropout request
@@ -455,6 +485,11 @@ class HipEnsemblePredictor(object):
         """``(map, target, base)`` of validated arguments (``CnnEnsemble.occlusion``) over the ``k`` members and
         their weights."""
         return occlusion_state(self, patch, stride, fill, "proba", self.k, self.weight).run(self, x, target)
+
+    def rise(self, x, target, masks, cells, p, seed, fill):
+        """``(map, target, base)`` of validated arguments (``CnnEnsemble.rise``) over the ``k`` members and their
+        weights."""
+        return rise_state(self, masks, cells, p, seed, fill, "proba", self.k, self.weight).run(self, x, target)
 
     def gradcam(self, x, target, score, relu):
         """``(map, target, base)`` of validated arguments (``CnnEnsemble.gradcam``) over the ``k`` members and

@@ -441,6 +441,138 @@ def occlusion_by_views(scores, x, target, patch, stride, fill, batch, rows=4096)
     return (np.repeat(base, Cc) - occluded).reshape(n, Gh, Gw), tgt, base
 
 
+RISE_MAX_MASKS = 8192        # RISE_MAX_MASKS of csrc/hip/cnn_rise.hip
+RISE_MAX_CELLS = 16          # RISE_MAX_CELLS of csrc/hip/cnn_rise.hip
+RISE_KEY = 0x52495345        # hash4 counter of the mask key ("RISE")
+
+
+def rise_check(input_shape, n, masks, cells, p, seed, batch):
+    """The validated ``(masks, cells, p, seed)`` of a RISE request over ``n`` images of ``input_shape``
+    ``(H, W, C)``, before any forward runs: ``masks`` an int in ``1..8192``, ``cells`` an int in ``2..16`` and at
+    most ``min(H, W)``, ``0 < p < 1``, ``seed`` an int in ``[0, 2^32)``, ``n * masks < 2^31``, ``batch`` a positive
+    int. ``ValueError`` on anything else."""
+    H, W = int(input_shape[0]), int(input_shape[1])
+    if not _is_int(masks) or not 1 <= int(masks) <= RISE_MAX_MASKS:
+        raise ValueError("rise: masks must be an integer in [1, {}], got {!r}".format(RISE_MAX_MASKS, masks))
+    if not _is_int(cells) or not 2 <= int(cells) <= min(RISE_MAX_CELLS, H, W):
+        raise ValueError("rise: cells must be an integer in [2, min({}, H, W) = {}], got {!r}".format(
+            RISE_MAX_CELLS, min(RISE_MAX_CELLS, H, W), cells))
+    if isinstance(p, (bool, np.bool_)) or not isinstance(p, (int, float, np.integer, np.floating)) \
+            or not 0.0 < float(p) < 1.0:
+        raise ValueError("rise: p must be a number in (0, 1), got {!r}".format(p))
+    if not _is_int(seed) or not 0 <= int(seed) < 2 ** 32:
+        raise ValueError("rise: seed must be an integer in [0, 2^32), got {!r}".format(seed))
+    if not _is_int(batch) or int(batch) < 1:
+        raise ValueError("batch must be a positive integer")
+    if int(n) * int(masks) >= 2 ** 31:
+        raise ValueError("rise: {} images x {} masks, fewer than 2^31 items".format(n, masks))
+    return int(masks), int(cells), float(p), int(seed)
+
+
+def rise_threshold(p):
+    """``uint32(p * 2^32)``: a grid bit is 1 iff its draw is below this."""
+    return int(float(p) * 4294967296.0) & 0xFFFFFFFF
+
+
+def rise_inv(masks, p):
+    """``1 / (masks * p)`` in fp64, the map's normalisation."""
+    return 1.0 / (float(masks) * float(p))
+
+
+def rise_masks(input_shape, masks, cells, p, seed, first=0):
+    """fp32 ``[masks, H, W]``: the masks ``first .. first + masks - 1`` of a RISE setting, shared by all images;
+    mask ``i`` is a function of ``(seed, i, cells, p, H, W)`` only. With ``s = cells``, ``ch = ceil(H / s)``,
+    ``cw = ceil(W / s)``, ``thr = uint32(p * 2^32)`` and ``k_i = hash4(seed, i, RISE_KEY, 0)`` (``utils.rng``): the
+    grid bit ``g(a, b) = 1`` iff ``hash4(k_i, a, b, 1) < thr`` for ``a, b`` in ``0..s+1``; the offsets
+    ``oy = hash4(k_i, 0, 0, 2) mod ch``, ``ox = hash4(k_i, 0, 0, 3) mod cw``; for pixel ``(y, x)``, ``Y = y + oy``,
+    ``a = Y // ch``, ``ty = fp32(Y - a * ch) / fp32(ch)`` (``X``, ``b``, ``tx`` likewise) and
+    ``M[y, x] = top + ty * (bot - top)`` with ``top = g(a, b) + tx * (g(a, b+1) - g(a, b))`` and ``bot`` the same in
+    row ``a + 1`` -- all in fp32, every product and sum rounded separately (``gt_rise_views`` / ``gt_rise_masks``
+    are the device twins, tests/rise_ref.py the loop oracle)."""
+    from ..utils.rng import hash4
+    H, W = int(input_shape[0]), int(input_shape[1])
+    s = int(cells)
+    ch, cw = -(-H // s), -(-W // s)
+    f32 = np.float32
+    i = np.arange(int(first), int(first) + int(masks), dtype=np.uint64)
+    key = hash4(int(seed), i, RISE_KEY, 0)
+    ab = np.arange(s + 2, dtype=np.uint64)
+    g = (hash4(key[:, None, None], ab[None, :, None], ab[None, None, :], 1)
+         < np.uint64(rise_threshold(p))).astype(f32)                               # [masks, s + 2, s + 2]
+    oy = (hash4(key, 0, 0, 2) % np.uint64(ch)).astype(np.int64)
+    ox = (hash4(key, 0, 0, 3) % np.uint64(cw)).astype(np.int64)
+    Y = np.arange(H)[None, :] + oy[:, None]                                        # [masks, H]
+    X = np.arange(W)[None, :] + ox[:, None]                                        # [masks, W]
+    a, b = Y // ch, X // cw
+    ty = ((Y - a * ch).astype(f32) / f32(ch))[:, :, None]
+    tx = ((X - b * cw).astype(f32) / f32(cw))[:, None, :]
+    m = np.arange(len(i))[:, None, None]
+    a, b = a[:, :, None], b[:, None, :]
+    g00, g01, g10, g11 = g[m, a, b], g[m, a, b + 1], g[m, a + 1, b], g[m, a + 1, b + 1]
+    top = g00 + tx * (g01 - g00)
+    bot = g10 + tx * (g11 - g10)
+    return (top + ty * (bot - top)).astype(f32, copy=False)
+
+
+def rise_views(x, M, fill):
+    """The masked copies ``[n, k, H, W, C]`` of fp32 images ``x [n, H, W, C]`` under masks ``M [k, H, W]``:
+    ``fill[c] + M[y, x] * (img[y, x, c] - fill[c])`` in fp32, the difference, the product and the sum rounded
+    separately."""
+    f = occlusion_fill(fill, x.shape[3])
+    x = np.asarray(x, np.float32)
+    return f + M[None, :, :, :, None] * (x[:, None] - f)
+
+
+def rise_by_views(scores, x, target, masks, cells, p, seed, fill, batch, rows=4096):
+    """The RISE map by :func:`rise_masks` and :func:`rise_views`: ``scores(images [k, H, W, C])`` returns
+    ``(score, proba)``, fp32 ``[k, classes]`` each, ``batch`` rows per forward (as in :func:`occlusion_by_views`).
+    Returns ``(map fp32 [n, H, W], target int64 [n], base fp32 [n])`` with
+    ``map[r] = (sum_i s_{r,i} M_i) * inv`` accumulated in fp64 and rounded once, ``s_{r,i}`` the score of the
+    target of ``V_i(x[r])`` and ``inv = 1 / (masks * p)``.
+
+    The copies of all images form one sequence of ``n * masks`` rows, item ``r * masks + i``; it is produced in
+    pieces of a multiple of ``batch`` rows (about ``rows``), so every forward holds the rows it would hold if the
+    whole sequence were given to ``scores`` at once."""
+    n, H, W = x.shape[0], x.shape[1], x.shape[2]
+    sc, pr = scores(x)
+    tgt = np.argmax(pr, axis=1).astype(np.int64) if target is None else target
+    base = np.asarray(sc, np.float32)[np.arange(n), tgt]
+    piece = int(batch) * max(1, int(rows) // int(batch))
+    acc = np.zeros((n, H * W), np.float64)
+    cache = {}                                           # first mask of a block of masks -> [<= piece, H, W]
+
+    def block(i0):
+        if i0 not in cache:
+            cache.clear()
+            cache[i0] = rise_masks(x.shape[1:], min(piece, masks - i0), cells, p, seed, first=i0)
+        return cache[i0]
+    for w0 in range(0, n * masks, piece):
+        k = min(piece, n * masks - w0)
+        views = np.empty((k,) + x.shape[1:], np.float32)
+        used, j = [], 0
+        while j < k:                                     # runs of one image inside one block of masks
+            r, i = divmod(w0 + j, masks)
+            i0 = i // piece * piece
+            cnt = min(k - j, masks - i, i0 + piece - i)
+            Mb = block(i0)[i - i0:i - i0 + cnt]
+            views[j:j + cnt] = rise_views(x[r:r + 1], Mb, fill)[0]
+            used.append((r, j, Mb))
+            j += cnt
+        sv = np.asarray(scores(views)[0], np.float32)
+        for r, j, Mb in used:
+            s = sv[j:j + len(Mb), tgt[r]].astype(np.float64)
+            M64 = Mb.reshape(len(Mb), -1).astype(np.float64)
+            for t in range(len(Mb)):                     # ascending i; every product is exact in fp64
+                acc[r] += s[t] * M64[t]
+    return (acc * rise_inv(masks, p)).astype(np.float32).reshape(n, H, W), tgt, base
+
+
+def rise_check_hip(classes):
+    """The ``ValueError`` of more classes than the HIP head kernels take, before a predictor is built."""
+    if classes > 16:
+        raise ValueError("HIP head kernel supports at most 16 classes")
+
+
 def predict_batch(batch):
     """Rows per launch of the HIP predictor: ``batch`` rounded up to a multiple of 32, at least 32 and
     at most 256 (the cap of ``HipPopJob.eval_batch``)."""
@@ -628,6 +760,41 @@ class CnnClassifier(object):
                 logits, proba = self._torch_predict(images, dev, int(batch), torch.float32)
                 return (logits if score == "logit" else proba), proba
             res = occlusion_by_views(scores, x, target, patch, stride, fill, int(batch))
+        else:
+            raise ValueError("unknown backend {!r}".format(backend))
+        return (res[0], {"target": res[1], "base": res[2]}) if return_info else res[0]
+
+    def rise(self, x, target=None, masks=2048, cells=7, p=0.5, seed=0, fill=0.0, score="proba", device=None,
+             batch=256, backend=None, return_info=False):
+        """RISE saliency (Petsiuk et al., randomized input sampling) of ``x`` ``[n, H, W, C]`` (or one image): fp32
+        ``[n, H, W]`` with ``map[r] = (sum_i s_{r,i} M_i) / (masks * p)``, where the ``masks`` random soft masks
+        ``M_i`` (:func:`rise_masks`: a ``cells`` x ``cells`` grid of bits set with probability ``p``, upsampled
+        bilinearly under a random shift; functions of ``seed``, shared by all images) blend the image with ``fill``
+        (:func:`rise_views`) and ``s`` is the probability (``score="proba"``) or the logit (``"logit"``) of the
+        target class of the blended image. Per pixel, by perturbation alone: no gradient is taken.
+
+        ``target``, ``fill``, ``return_info`` and ``device`` / ``backend`` / ``batch`` as in :meth:`occlusion`. The
+        CPU or ``backend="torch"`` feeds the views to the stock-torch forward and accumulates in fp64
+        (:func:`rise_by_views`); a ``cuda`` device uploads every image once, blends on the device
+        (``gt_rise_views``), packs the copies densely into launches of ``EB`` rows, keeps one score per copy
+        (``gt_head_rise``) and forms ``scores x masks`` on the matrix cores (``gt_rise_accumulate``)."""
+        if score not in OCC_SCORES:
+            raise ValueError("score {!r}: expected one of {}".format(score, OCC_SCORES))
+        x = self._check_x(x)
+        masks, cells, p, seed = rise_check(self.input_shape, x.shape[0], masks, cells, p, seed, batch)
+        fill = occlusion_fill(fill, self.input_shape[2])
+        target = occlusion_targets(target, x.shape[0], self.classes, "rise")
+        dev = torch.device("cpu" if device is None else device)
+        if backend is None:
+            backend = "hip" if dev.type == "cuda" else "torch"
+        if backend == "hip":
+            rise_check_hip(self.classes)
+            res = self.hip_predictor(dev, batch).rise(x, target, masks, cells, p, seed, fill, score)
+        elif backend == "torch":
+            def scores(images):
+                logits, proba = self._torch_predict(images, dev, int(batch), torch.float32)
+                return (logits if score == "logit" else proba), proba
+            res = rise_by_views(scores, x, target, masks, cells, p, seed, fill, int(batch))
         else:
             raise ValueError("unknown backend {!r}".format(backend))
         return (res[0], {"target": res[1], "base": res[2]}) if return_info else res[0]
@@ -1180,6 +1347,128 @@ def occlusion_state(pred, patch, stride, fill, score, G, weight):
     return st
 
 
+class RiseState(object):
+    """What a HIP predictor (``HipPredictor`` or ``HipEnsemblePredictor``) adds for one RISE setting
+    ``(masks, cells, p, seed, fill, score)``: the raw buffer of up to ``EB`` fp32 images in the staging tensor's
+    layout, the fill value, the three bf16 planes of every mask ``[3][Pp][Kp]`` (``gt_rise_masks``, once), the
+    scores ``S [EB][Kp]`` (zeroed once: ``gt_head_rise`` writes the real entries only) and the arguments of
+    ``gt_rise_views``, ``gt_head_occlusion`` phase 0 (target and base score per image), ``gt_head_rise`` and
+    ``gt_rise_accumulate``. The unit of work is the item ``w = r * masks + i``; items are packed densely into
+    launches of ``EB`` rows. The predictor's job, evaluation launches and gather table are used as they are."""
+
+    def __init__(self, pred, masks, cells, p, seed, fill, score, G, weight):
+        K, job, stage = pred.K, pred.job, pred.stage
+        h, w, c = pred.hwc
+        EB, dev = pred.EB, pred.device
+        self.masks, self.P = masks, h * w
+        self.Kp, self.Pp = (masks + 31) // 32 * 32, (h * w + 63) // 64 * 64
+        self.raw = torch.zeros((EB,) + tuple(stage.shape[1:]), dtype=torch.float32, device=dev)
+        f = torch.zeros(int(stage.shape[3]), dtype=torch.float32)
+        f[:c] = torch.from_numpy(occlusion_fill(fill, c))
+        self.fill = f.to(dev)
+        self.weight = weight
+        self.tgt = torch.empty(EB, dtype=torch.int32, device=dev)
+        self.base = torch.empty(EB, dtype=torch.float32, device=dev)
+        self.S = torch.zeros((EB, self.Kp), dtype=torch.float32, device=dev)
+        self.planes = torch.empty((3, self.Pp, self.Kp), dtype=torch.int16, device=dev)
+        self.map = torch.empty((EB, self.P), dtype=torch.float32, device=dev)
+        self.scores = None           # [n, masks] on the device: the scores of the last run
+        thr = rise_threshold(p)
+        ma = K.RiseMaskArgs()
+        ma.planes, ma.masks, ma.Kp, ma.cells = self.planes.data_ptr(), masks, self.Kp, cells
+        ma.seed, ma.thr, ma.Hr, ma.Wr, ma.Pp = seed, thr, h, w, self.Pp
+        K.check(job.L.gt_rise_masks(ma, job._stream()), "rise_masks")
+        va = K.RiseViewArgs()
+        va.raw, va.out, va.fill = self.raw.data_ptr(), stage.data_ptr(), self.fill.data_ptr()
+        va.masks, va.cells, va.seed, va.thr = masks, cells, seed, thr
+        va.rows = va.cap = EB
+        va.Hp, va.Wp, va.Cp = (int(d) for d in stage.shape[1:])
+        va.Hr, va.Wr, va.Cr = h, w, c
+        va.prec = 1 if stage.dtype == torch.float32 else 0
+        self.view_args = va
+        b = K.HeadOcclusionArgs()                        # phase 0 only: the map is never written
+        b.plog, b.b2, b.weight = pred.df.plog, job.views["b2"][0].data_ptr(), weight.data_ptr()
+        b.tgt, b.base, b.map = self.tgt.data_ptr(), self.base.data_ptr(), 0
+        b.G, b.B, b.Up, b.C = G, EB, job.Up, pred.classes
+        b.Cc, b.w0, b.phase, b.logit = masks, 0, 0, 1 if score == "logit" else 0
+        self.base_head = b
+        a = K.HeadRiseArgs()
+        a.plog, a.b2, a.weight = b.plog, b.b2, b.weight
+        a.tgt, a.S = self.tgt.data_ptr(), self.S.data_ptr()
+        a.G, a.B, a.Up, a.C = G, EB, job.Up, pred.classes
+        a.masks, a.Kp, a.logit = masks, self.Kp, b.logit
+        self.head = a
+        g = K.RiseAccArgs()
+        g.planes, g.S, g.out = self.planes.data_ptr(), self.S.data_ptr(), self.map.data_ptr()
+        g.masks, g.Kp, g.P, g.Pp = masks, self.Kp, self.P, self.Pp
+        g.inv = float(np.float32(rise_inv(masks, p)))
+        self.acc = g
+
+    def upload(self, chunk, target, hwc):
+        """``chunk`` [m <= EB, H, W, C] host fp32 into the raw buffer and its targets (int64 ``[m]``, or ``None``:
+        -1, the label) into ``tgt``. Rows past ``m`` are never read."""
+        m = chunk.shape[0]
+        h, w, c = hwc
+        self.raw[:m, :h, :w, :c].copy_(torch.from_numpy(chunk).to(self.raw.device))
+        if target is None:
+            self.tgt.fill_(-1)
+        else:
+            self.tgt[:m].copy_(torch.from_numpy(target.astype(np.int32)).to(self.tgt.device))
+
+    def launch(self, pred, m, w0, base):
+        """One launch set on the current stream: the items from ``w0`` (``base``: the ``m`` images as they are)
+        -> the staging tensor -> the predictor's forward at ``EB`` rows -> ``tgt`` / ``base`` or ``S``."""
+        job, K = pred.job, pred.K
+        s = job._stream()
+        va = self.view_args
+        va.m, va.w0, va.base = m, w0, 1 if base else 0
+        K.check(job.L.gt_rise_views(va, s), "rise_views")
+        job._run_fwd(s, pred.ops)
+        K.check(job.L.gt_dense_fwd(pred.df, s), "dense_fwd(rise)")
+        if base:
+            self.base_head.m = m
+            K.check(job.L.gt_head_occlusion(self.base_head, s), "head_occlusion(rise)")
+        else:
+            self.head.m, self.head.w0 = m, w0
+            K.check(job.L.gt_head_rise(self.head, s), "head_rise")
+
+    def run(self, pred, x, target):
+        """``x`` [n, H, W, C] host fp32 -> ``(map [n, H, W], target int64 [n], base fp32 [n])`` as host arrays:
+        per group of ``EB`` images one upload, one base launch set, ``ceil(m * masks / EB)`` packed launch sets
+        and one accumulate launch; the results gather on the device and are read back once."""
+        n, EB, masks, dev = x.shape[0], pred.EB, self.masks, pred.device
+        h, w, _ = pred.hwc
+        job, K = pred.job, pred.K
+        with torch.cuda.device(dev):
+            out = torch.empty((n, self.P), dtype=torch.float32, device=dev)
+            tgt = torch.empty(n, dtype=torch.int32, device=dev)
+            base = torch.empty(n, dtype=torch.float32, device=dev)
+            self.scores = torch.empty((n, masks), dtype=torch.float32, device=dev)
+            for s in range(0, n, EB):
+                m = min(EB, n - s)
+                self.upload(x[s:s + m], None if target is None else target[s:s + m], pred.hwc)
+                self.launch(pred, m, 0, True)
+                for w0 in range(0, m * masks, EB):
+                    self.launch(pred, m, w0, False)
+                self.acc.m = m
+                K.check(job.L.gt_rise_accumulate(self.acc, job._stream()), "rise_accumulate")
+                out[s:s + m].copy_(self.map[:m])
+                tgt[s:s + m].copy_(self.tgt[:m])
+                base[s:s + m].copy_(self.base[:m])
+                self.scores[s:s + m].copy_(self.S[:m, :masks])
+            return (out.cpu().numpy().reshape(n, h, w), tgt.cpu().numpy().astype(np.int64), base.cpu().numpy())
+
+
+def rise_state(pred, masks, cells, p, seed, fill, score, G, weight):
+    """The cached :class:`RiseState` of a predictor (its ``_rise`` dict) for one setting."""
+    key = (masks, cells, p, seed, tuple(float(v) for v in fill), score)
+    st = pred._rise.get(key)
+    if st is None:
+        with torch.cuda.device(pred.device):
+            st = pred._rise[key] = RiseState(pred, masks, cells, p, seed, fill, score, G, weight)
+    return st
+
+
 def cam_wbar(pred, G):
     """``wbar [G][Cp][Up]`` of a HIP predictor, ``W1`` summed over the real pixels of the last feature map
     (``gt_cam_w1sum``): a constant of the loaded parameters, computed on the first Grad-CAM request."""
@@ -1629,6 +1918,7 @@ class HipPredictor(object):
             self.head = hp
         self._tta = {}               # views -> TtaState, created on first use
         self._occ = {}               # (patch, stride, fill, score) -> OcclusionState, created on first use
+        self._rise = {}              # (masks, cells, p, seed, fill, score) -> RiseState, created on first use
         self._one = None             # the one member's weight 1.0 on the device, for the occlusion head
         self._cam = {}               # (score, relu) -> GradcamState, created on first use
         self._cam_wbar = None        # W1 summed over the real pixels (cam_wbar), on the first Grad-CAM request
@@ -1666,6 +1956,13 @@ class HipPredictor(object):
         if self._one is None:
             self._one = torch.ones(1, dtype=torch.float32, device=self.device)
         return occlusion_state(self, patch, stride, fill, score, 1, self._one).run(self, x, target)
+
+    def rise(self, x, target, masks, cells, p, seed, fill, score):
+        """``(map, target, base)`` of validated arguments (``CnnClassifier.rise``): one member of weight 1.0
+        (``1.0f * p`` is ``p``)."""
+        if self._one is None:
+            self._one = torch.ones(1, dtype=torch.float32, device=self.device)
+        return rise_state(self, masks, cells, p, seed, fill, score, 1, self._one).run(self, x, target)
 
     def gradcam(self, x, target, score, relu):
         """``(map, target, base)`` of validated arguments (``CnnClassifier.gradcam``): one member of weight 1.0

@@ -278,6 +278,36 @@ class OccludeArgs(C.Structure):
                 ("prec", I), ("base", I)]
 
 
+RISE_MAX_MASKS = 8192   # masks of one RISE request at most (csrc/hip/cnn_rise.hip RISE_MAX_MASKS)
+RISE_MAX_CELLS = 16     # cells per side of a RISE grid at most (csrc/hip/cnn_rise.hip RISE_MAX_CELLS)
+
+
+class RiseViewArgs(C.Structure):
+    """csrc/hip/cnn_rise.hip RiseViewArgs: the masked copies of a group of raw fp32 images, packed item by item
+    into the staging tensor (gt_rise_views)."""
+    _fields_ = [("raw", P), ("out", P), ("fill", P), ("m", I), ("w0", I), ("masks", I), ("cells", I),
+                ("seed", C.c_uint), ("thr", C.c_uint), ("rows", I), ("cap", I), ("Hp", I), ("Wp", I), ("Hr", I),
+                ("Wr", I), ("Cp", I), ("Cr", I), ("prec", I), ("base", I)]
+
+
+class RiseMaskArgs(C.Structure):
+    """csrc/hip/cnn_rise.hip RiseMaskArgs: the three bf16 planes of every mask of a setting (gt_rise_masks)."""
+    _fields_ = [("planes", P), ("masks", I), ("Kp", I), ("cells", I), ("seed", C.c_uint), ("thr", C.c_uint),
+                ("Hr", I), ("Wr", I), ("Pp", I)]
+
+
+class RiseAccArgs(C.Structure):
+    """csrc/hip/cnn_rise.hip RiseAccArgs: scores x masks -> the maps of a group of images (gt_rise_accumulate)."""
+    _fields_ = [("planes", P), ("S", P), ("out", P), ("m", I), ("masks", I), ("Kp", I), ("P", I), ("Pp", I),
+                ("inv", C.c_float)]
+
+
+class HeadRiseArgs(C.Structure):
+    """csrc/hip/cnn_dense.hip HeadRiseArgs: the target's score of every masked copy of a launch (gt_head_rise)."""
+    _fields_ = [("plog", P), ("b2", P), ("weight", P), ("tgt", P), ("S", P), ("G", I), ("B", I), ("Up", I),
+                ("C", I), ("m", I), ("masks", I), ("Kp", I), ("w0", I), ("logit", I)]
+
+
 class DenseDgradArgs(C.Structure):
     _fields_ = [("dH", P), ("wt", P), ("dx", P), ("G", I), ("B", I), ("Fp", I), ("Up", I), ("prec", I),
                 ("wps", C.c_long), ("unpool_mask", P), ("unpool_x0", P), ("unpool_x1", P), ("unpool_sel", P),
@@ -448,6 +478,18 @@ def lib():
         L.gt_sizeof_occlude_args.restype = C.c_size_t
         assert L.gt_sizeof_occlude_args() == C.sizeof(OccludeArgs), "OccludeArgs ABI mismatch"
         assert L.gt_occlude_max_cells() == OCC_MAX_CELLS, "OCC_MAX_CELLS mismatch"
+        for fname, sname, st in (("gt_rise_views", "rise_view", RiseViewArgs),
+                                 ("gt_rise_masks", "rise_mask", RiseMaskArgs),
+                                 ("gt_rise_accumulate", "rise_acc", RiseAccArgs),
+                                 ("gt_head_rise", "head_rise", HeadRiseArgs)):
+            fn = getattr(L, fname)
+            fn.argtypes = [C.POINTER(st), P]
+            fn.restype = I
+            size = getattr(L, "gt_sizeof_{}_args".format(sname))
+            size.restype = C.c_size_t
+            assert size() == C.sizeof(st), st.__name__ + " ABI mismatch"
+        assert L.gt_rise_max_masks() == RISE_MAX_MASKS, "RISE_MAX_MASKS mismatch"
+        assert L.gt_rise_max_cells() == RISE_MAX_CELLS, "RISE_MAX_CELLS mismatch"
         L.gt_adam_segments.argtypes = [C.POINTER(AdamArgs), I, P]
         L.gt_adam_segments.restype = I
         L.gt_step_begin.argtypes = [P, P]

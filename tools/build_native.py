@@ -56,6 +56,7 @@ TARGETS = {
 HIP_EXTRA_FLAGS = {
     "cnn_head_mc.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
     "cnn_saliency.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+    "cnn_rise.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
 }
 
 

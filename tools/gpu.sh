@@ -21,6 +21,7 @@
 #   bash tools/gpu.sh cnn-distill             soft targets: step time of the parent tree (ab_old/) / off / label_smoothing / a target table, the head kernels' time from a kernel trace run of its own, the distillation record (GROUPS_LIST= REPS= PROF_GROUPS= OUT= ACC=0)
 #   bash tools/gpu.sh cnn-tta                 predict(tta=...): views and mean on the device vs V plain HIP predicts combined in numpy vs stock torch, classifier and k-ensemble (ROWS= FIT_ROWS= K= REPS= OUT=)
 #   bash tools/gpu.sh cnn-occlusion           occlusion(): copies built and packed on the device vs occlusion_views in numpy + plain HIP predicts vs stock torch, classifier and k-ensemble (ROWS= FIT_ROWS= K= REPS= OUT= TIME=)
+#   bash tools/gpu.sh cnn-rise                rise(): copies blended and packed on the device + gt_rise_accumulate vs rise_views in numpy + plain HIP predicts vs stock torch, classifier and k-ensemble; the kernels' device time by a kernel trace run of its own (ROWS= MASKS= FIT_ROWS= K= REPS= OUT= TIME=)
 #   bash tools/gpu.sh cnn-gradcam             gradcam(): forward + gt_head_gradcam vs plain HIP predict (the floor) vs stock-torch autograd vs occlusion(patch=4), classifier and k-ensemble; the new kernels' device time by events and by a kernel trace run of its own (ROWS= OCC_ROWS= FIT_ROWS= K= REPS= OUT= TIME=)
 #   bash tools/gpu.sh cnn-saliency            saliency(): masked forward + backward chain + gt_conv_in_dgrad vs plain HIP predict (the floor) vs the stock-torch backend, integrated gradients on IG_ROWS rows, classifier and k-ensemble; the kernels' device time by a kernel trace run of its own (ROWS= IG_ROWS= STEPS= FIT_ROWS= K= REPS= OUT= TIME=)
 #   bash tools/gpu.sh cnn-mc                predict_mc(): forward + gt_head_mc vs plain HIP predict (the floor) vs the stock-torch backend, classifier and k-ensemble; the kernel's device time by a kernel trace run of its own (ROWS= SAMPLES= FIT_ROWS= K= REPS= OUT= TIME=)
@@ -219,6 +220,20 @@ cnn-occlusion)
   timeout -k 10 ${TIME:-900} python -u tools/bench_cnn_occlusion.py --rows ${ROWS:-1000} --fit-rows ${FIT_ROWS:-2000} \
     --k ${K:-4} --reps ${REPS:-5} ${OCC_ARGS:-} > $out/bench.json 2> $out/bench.err; rc=$?
   [ $rc -eq 0 ] && tail -1 $out/bench.json | cut -c1-8000 || { tail -5 $out/bench.err; cut -c1-2000 $out/bench.json; }
+  exit $rc ;;
+cnn-rise)
+  # one line per finished case and the result line, then the chain's own durations from a kernel trace of one child
+  # run of its own (fits, then three rise calls and twenty plain launch sets per model); files are kept under $OUT
+  out=${OUT:-/tmp/cnn_rise}; heartbeat; mkdir -p $out; rocprof_env; rm -rf /tmp/prof_rise
+  timeout -k 10 ${TIME:-900} python -u tools/bench_cnn_rise.py --rows ${ROWS:-1000} --masks ${MASKS:-2048} \
+    --fit-rows ${FIT_ROWS:-2000} --k ${K:-4} --reps ${REPS:-5} ${RISE_ARGS:-} > $out/bench.json 2> $out/bench.err &&
+  tail -1 $out/bench.json | cut -c1-8000 &&
+  timeout -k 10 300 rocprofv3 --kernel-trace --stats -d /tmp/prof_rise -o run --output-format csv -- \
+    python3 tools/bench_cnn_rise.py --trace --rows ${TRACE_ROWS:-64} --masks ${MASKS:-2048} \
+    --fit-rows ${FIT_ROWS:-2000} --k ${K:-4} ${RISE_ARGS:-} > $out/prof.log 2>&1 &&
+  find /tmp/prof_rise -name "*kernel_stats.csv" -exec cp {} $out/kernel_stats.csv \; &&
+  grep -E "Name|rise|head_occlusion|head_predict|head_ensemble|conv_fast|dense_fwd" $out/kernel_stats.csv | cut -c1-300; rc=$?
+  [ $rc -eq 0 ] || { tail -5 $out/bench.err $out/prof.log 2>/dev/null; cut -c1-2000 $out/bench.json; }
   exit $rc ;;
 cnn-gradcam)
   # the result line, then the new kernels' own durations from a kernel trace of one child run of its own (fits,
