@@ -26,6 +26,7 @@
 #include <cstring>
 
 #include "common.h"
+#include "cnn_mix.h"
 
 #define HEAD_MAXC_FWD 16
 #define ADAM_B1 0.9f
@@ -499,6 +500,115 @@ __global__ void __launch_bounds__(64) head_fwd_soft_kernel(HeadSoftArgs sa) {
   const float inv_b = (b < nv && nn > 0) ? 1.0f / nn : 0.f;
   if (a.loss_ce) {
     // exact for any target row that sums to 1
+    for (int c = 0; c < C; ++c) dz[c] = (p[c] - tv[c]) * inv_b;
+  } else {
+    // dL/dp_c = (pc - t_c)/(pc(1-pc)) / C inside the clip range, 0 where clipped
+    float dp[HEAD_MAXC], s = 0.f;
+    for (int c = 0; c < C; ++c) {
+      const float yc = tv[c];
+      const bool inside = p[c] >= CLIP_EPS && p[c] <= 1.f - CLIP_EPS;
+      const float pc = fminf(fmaxf(p[c], CLIP_EPS), 1.f - CLIP_EPS);
+      dp[c] = inside ? (pc - yc) / (pc * (1.f - pc)) / C : 0.f;
+      s += p[c] * dp[c];
+    }
+    for (int c = 0; c < C; ++c) dz[c] = p[c] * (dp[c] - s) * inv_b;
+  }
+}
+
+// Mixup / CutMix training head (models/cnn_engine.py "The mixed step"): HeadSoftArgs plus what the step's draw
+// needs. The target of a real row b of an applied step is fp32(lam t_b) + fp32(lam1 t_p), t_b and t_p the
+// target rows of b and of its partner p(b) under whichever source HeadSoftArgs names (hard labels are
+// t_on = 1, t_off = 0). Training only.
+struct HeadMixArgs {
+  HeadSoftArgs s;
+  const int* fold_ids;     // [G] or null (then: the group index)
+  const unsigned* seeds;   // [G] per-group keys or null -> seed
+  unsigned seed;
+  int kind;                // 0 mixup, 1 cutmix
+  int alpha;               // 1 .. MIX_MAX_ALPHA
+  unsigned p24;            // round(prob * 2^24), 1 .. 2^24
+  int Hr, Wr;              // cutmix: the real image (the box and its area)
+  float inv_hw;            // cutmix: fp32(1) / fp32(Hr * Wr)
+};
+
+// head_fwd_soft_kernel with the mixed target row. The draw is recomputed from (key, global step): wave-uniform
+// integer work (cnn_mix.h), done first so that the partner's sid -> label / table row chain is issued beside
+// the row's own, ahead of the partial-logit loads and the reduction. The reduction, the softmax and both dz
+// expressions repeat head_fwd_soft_kernel's code operation for operation: on a step that is not applied (and
+// on a padding row) tv is the row's own target and dz is what gt_head_soft writes, bit for bit.
+__global__ void __launch_bounds__(64) head_fwd_mix_kernel(HeadMixArgs ma) {
+  const HeadSoftArgs& sa = ma.s;
+  const HeadArgs& a = sa.h;
+  const int idx = blockIdx.x, lane = threadIdx.x;
+  const int g = idx / a.B, b = idx % a.B;
+  const int C = a.C, nt = a.Up / 16;
+  const int step = a.st->cur_step;
+  const int nv = a.valid ? a.valid[(long)step * a.G + g] : a.B;
+  const uint32_t fid = ma.fold_ids ? (uint32_t)ma.fold_ids[g] : (uint32_t)g;
+  const uint32_t key = (ma.seeds ? ma.seeds[g] : ma.seed) ^ (fid * 0x632be5abU);
+  const uint32_t gs = (uint32_t)a.st->global_step;
+  const int nvc = nv < a.B ? nv : a.B;             // the partner stays inside this group's rows of the table
+  const MixDraw d = mix_draw(key, gs, nvc, ma.alpha, ma.p24);
+  const bool mixed = d.applied && b < nvc;
+  const int pb = mixed ? (int)(((uint32_t)b + d.o) % (uint32_t)nvc) : b;
+  const long sid = a.gather[((long)step * a.G + g) * a.B + b];
+  const long sidp = a.gather[((long)step * a.G + g) * a.B + pb];
+  float tv[HEAD_MAXC], tp[HEAD_MAXC];
+  if (sa.soft) {
+    const float* tr = sa.soft + sid * C;
+    const float* trp = sa.soft + sidp * C;
+#pragma unroll
+    for (int c = 0; c < HEAD_MAXC; ++c) { tv[c] = tr[min(c, C - 1)]; tp[c] = trp[min(c, C - 1)]; }
+  } else {
+    const int y = (int)a.labels[sid], yp = (int)a.labels[sidp];
+#pragma unroll
+    for (int c = 0; c < HEAD_MAXC; ++c) {
+      tv[c] = (c == y) ? sa.t_on : sa.t_off;
+      tp[c] = (c == yp) ? sa.t_on : sa.t_off;
+    }
+  }
+  float acc[HEAD_MAXC];
+  const float* pl = a.plog + ((long)g * nt * a.B + b) * C;
+#pragma unroll
+  for (int c = 0; c < HEAD_MAXC; ++c) acc[c] = 0.f;
+  for (int t = lane; t < nt; t += 64) {
+    float v[HEAD_MAXC];
+#pragma unroll
+    for (int c = 0; c < HEAD_MAXC; ++c) v[c] = pl[(long)t * a.B * C + min(c, C - 1)];
+#pragma unroll
+    for (int c = 0; c < HEAD_MAXC; ++c) acc[c] += c < C ? v[c] : 0.f;
+  }
+#pragma unroll
+  for (int c = 0; c < HEAD_MAXC; ++c) {
+    if (c < C) {
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) acc[c] += __shfl_xor(acc[c], o);
+    }
+  }
+  if (lane != 0) return;
+  if (mixed) {
+    MixBox bx = {0, 0, 0, 0};
+    float lam, lam1;
+    if (ma.kind) bx = mix_box(key, gs, d.m, ma.Hr, ma.Wr);
+    mix_weights(ma.kind, d.m, bx, ma.Hr, ma.Wr, ma.inv_hw, lam, lam1);
+#pragma unroll
+    for (int c = 0; c < HEAD_MAXC; ++c) tv[c] = mix_blend(lam, tv[c], lam1, tp[c]);
+  }
+  float logit[HEAD_MAXC];
+  for (int c = 0; c < C; ++c) logit[c] = acc[c] + a.b2[(long)g * C + c];
+  float p[HEAD_MAXC];
+  float mx = -INFINITY;
+  for (int c = 0; c < C; ++c) mx = fmaxf(mx, logit[c]);
+  float z = 0.f;
+  for (int c = 0; c < C; ++c) { p[c] = expf(logit[c] - mx); z += p[c]; }
+  for (int c = 0; c < C; ++c) p[c] /= z;
+  float* dz = a.dz + ((long)g * a.B + b) * C;
+  // mean over the batch's real rows; padding rows of a short batch: zero weight
+  const int nn = a.valid_norm ? a.valid_norm[(long)step * a.G + g] : nv;
+  const float inv_b = (b < nv && nn > 0) ? 1.0f / nn : 0.f;
+  if (a.loss_ce) {
+    // exact for any target row that sums to 1. A mixed row does within one rounding per class: mixup's
+    // lam + lam1 is exactly 1 and cutmix's two weights add up to 1 within one rounding of each
     for (int c = 0; c < C; ++c) dz[c] = (p[c] - tv[c]) * inv_b;
   } else {
     // dL/dp_c = (pc - t_c)/(pc(1-pc)) / C inside the clip range, 0 where clipped
@@ -1690,6 +1800,28 @@ int gt_head_soft(const HeadSoftArgs* sa, hipStream_t stream) {
   return (int)hipGetLastError();
 }
 
+// The training head of a mixup / cutmix step: head_fwd_mix_kernel, then the unchanged head_bwd_kernel on the
+// embedded HeadArgs. Refuses what gt_head_soft refuses, a missing step state and the mix ranges.
+int gt_head_mix(const HeadMixArgs* ma, hipStream_t stream) {
+  if (!ma) return -4;
+  const HeadSoftArgs* sa = &ma->s;
+  const HeadArgs* a = &sa->h;
+  if (a->eval) return -1;                                               // training only
+  if (a->G < 1 || a->B < 1 || a->B > HEAD_MAXB || a->C < 1 || a->C > HEAD_MAXC) return -1;
+  if (a->Up < 16 || a->Up % 16) return -2;
+  if (!a->plog || !a->b2 || !a->labels || !a->gather || !a->dz || !a->st) return -3;
+  if (!a->h || !a->w2 || !a->dH || !a->gw2 || !a->gb2 || !a->gb1) return -3;     // head_bwd_kernel's operands
+  if (!sa->soft && !(finite_bits(sa->t_on) && finite_bits(sa->t_off))) return -5;
+  if (ma->kind != 0 && ma->kind != 1) return -8;
+  if (ma->alpha < 1 || ma->alpha > MIX_MAX_ALPHA) return -9;
+  if (ma->p24 < 1u || ma->p24 > MIX_ONE24) return -10;
+  if (ma->kind == 1 && (ma->Hr < 1 || ma->Wr < 1 || ma->Hr > 32767 || ma->Wr > 32767 || !finite_bits(ma->inv_hw)))
+    return -12;
+  hipLaunchKernelGGL(head_fwd_mix_kernel, dim3(a->G * a->B), dim3(64), 0, stream, *ma);
+  hipLaunchKernelGGL(head_bwd_kernel, dim3((a->Up + 63) / 64, a->G), dim3(256), 0, stream, *a);
+  return (int)hipGetLastError();
+}
+
 int gt_head_predict(const HeadPredictArgs* a, hipStream_t stream) {
   if (a->C < 1 || a->C > HEAD_MAXC || a->G < 1 || a->B < 1) return -1;
   if (a->Up < 16 || a->Up % 16) return -2;
@@ -1842,6 +1974,7 @@ int gt_adam_block_elems() { return ADAM_BLK; }
 size_t gt_sizeof_dense_fwd_args() { return sizeof(DenseFwdArgs); }
 size_t gt_sizeof_head_args() { return sizeof(HeadArgs); }
 size_t gt_sizeof_head_soft_args() { return sizeof(HeadSoftArgs); }
+size_t gt_sizeof_head_mix_args() { return sizeof(HeadMixArgs); }
 size_t gt_sizeof_head_predict_args() { return sizeof(HeadPredictArgs); }
 size_t gt_sizeof_head_ensemble_args() { return sizeof(HeadEnsembleArgs); }
 size_t gt_sizeof_head_tta_args() { return sizeof(HeadTtaArgs); }

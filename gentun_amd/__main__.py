@@ -194,6 +194,19 @@ def label_smoothing_setting(args):
     return eps
 
 
+def mix_setting(args):
+    """``TrainConfig.mix`` of ``--mix mixup|cutmix --mix-alpha A --mix-prob P`` (None without ``--mix``)."""
+    kind = getattr(args, "mix", None)
+    if not kind:
+        return None
+    from .models.cnn_engine import normalize_mix
+    try:
+        return normalize_mix({"kind": kind, "alpha": getattr(args, "mix_alpha", 1),
+                              "prob": getattr(args, "mix_prob", 1.0)})
+    except ValueError as exc:
+        raise SystemExit("--mix: {}".format(exc))
+
+
 def cmd_cnn(args):
     from . import GeneticCnnIndividual
     from .utils.data import make_glyph_classification, make_variant_classification
@@ -212,7 +225,8 @@ def cmd_cnn(args):
                  epochs=_ints(args.epochs), learning_rate=_floats(args.lr), batch_size=args.batch, loss=args.loss,
                  seed=args.seed, optimizer=args.optimizer, momentum=args.momentum, dtype=args.dtype,
                  reset=args.fold_reset, batching=args.batching, batch_norm=args.batch_norm,
-                 augment=augment_setting(args), label_smoothing=label_smoothing_setting(args))
+                 augment=augment_setting(args), label_smoothing=label_smoothing_setting(args),
+                 mix=mix_setting(args))
     keep = {}
     out = _run_search(args, GeneticCnnIndividual, x, y, extra, maximize=True, keep=keep)
     if out is not None and args.save_model:
@@ -348,6 +362,12 @@ def main(argv=None):
                    help="conv -> BatchNorm -> ReLU in every node (not in the reference network; off by default)")
     c.add_argument("--augment-shift", type=int, default=0, metavar="N",
                    help="training-time augmentation: random translation by up to N pixels with zero fill (0: off)")
+    c.add_argument("--mix", choices=("mixup", "cutmix"), default=None,
+                   help="mix every training batch and its targets with a partner row (off by default)")
+    c.add_argument("--mix-alpha", type=int, default=1, metavar="A",
+                   help="--mix: the mixing weight is Beta(A, A), A an integer from 1 to 8")
+    c.add_argument("--mix-prob", type=float, default=1.0, metavar="P",
+                   help="--mix: the share of training steps that are mixed, in (0, 1]")
     c.add_argument("--augment-flip", action="store_true",
                    help="training-time augmentation: random horizontal flip (off by default)")
     c.add_argument("--label-smoothing", type=float, default=0.0, metavar="EPS",

@@ -280,7 +280,9 @@ class GeneticCnnIndividual(Individual):
     images; ``{"shift": s, "flip": bool}`` = the Genetic-CNN paper's random translation
     with zero fill and random horizontal flip, re-drawn every step on the device) and
     ``label_smoothing`` (0.0 = hard labels; ``eps`` in (0, 1) = the training targets
-    ``1 - eps + eps / classes`` for the labelled class and ``eps / classes`` for the others).
+    ``1 - eps + eps / classes`` for the labelled class and ``eps / classes`` for the others) and
+    ``mix`` (None = off; ``{"kind": "mixup" | "cutmix", "alpha": 1..8, "prob": p}`` = every training
+    batch and its target rows mixed with a partner row, re-drawn every step on the device).
     """
 
     def __init__(self, x_train, y_train, genome=None, genes=None, crossover_rate=0.3, mutation_rate=0.1,
@@ -289,7 +291,7 @@ class GeneticCnnIndividual(Individual):
                  nfold=5, epochs=(3,), learning_rate=(1e-3,), batch_size=32,
                  loss='bce_compat', dtype='fp32', seed=0, backend=None, device=None, optimizer='adam',
                  momentum=0.9, reset='kernels', batching='keras', batch_norm=False, verbose=False,
-                 pad_images=True, augment=None, label_smoothing=0.0):
+                 pad_images=True, augment=None, label_smoothing=0.0, mix=None):
         if genome is None:
             genome = {'S_{}'.format(i + 1): k * (k - 1) // 2 for i, k in enumerate(nodes)}
         if genes is None:
@@ -328,6 +330,8 @@ class GeneticCnnIndividual(Individual):
         self.augment = None if augment is None else dict(augment)
         # label smoothing of the training targets (TrainConfig.label_smoothing; 0.0: off)
         self.label_smoothing = label_smoothing
+        # mixup / cutmix of the training batches: None or {"kind", "alpha", "prob"} (TrainConfig.mix)
+        self.mix = None if mix is None else dict(mix)
 
     @staticmethod
     def generate_random_genes(genome):
@@ -347,7 +351,7 @@ class GeneticCnnIndividual(Individual):
                                optimizer=self.optimizer, momentum=self.momentum, reset=self.reset,
                                batching=self.batching, batch_norm=self.batch_norm,
                                verbose=self.verbose, pad_images=self.pad_images, augment=self.augment,
-                               label_smoothing=self.label_smoothing)
+                               label_smoothing=self.label_smoothing, mix=self.mix)
 
     def cost(self):
         """Relative training cost (forward FLOPs/sample); LPT scheduling key."""
@@ -388,6 +392,7 @@ class GeneticCnnIndividual(Individual):
             'pad_images': self.pad_images,
             'augment': self.augment,
             'label_smoothing': self.label_smoothing,
+            'mix': self.mix,
         }
 
     def mutate(self):

@@ -29,7 +29,7 @@ class GeneticCnnModel(GentunModel):
                  dropout_probability, classes, nfold=5, epochs=(3,), learning_rate=(1e-3,), batch_size=32,
                  loss="bce_compat", dtype="fp32", seed=0, backend=None, device=None, fold_parallel=True,
                  optimizer="adam", momentum=0.9, reset="kernels", batching="keras", batch_norm=False,
-                 verbose=False, pad_images=True, augment=None, label_smoothing=0.0):
+                 verbose=False, pad_images=True, augment=None, label_smoothing=0.0, mix=None):
         super(GeneticCnnModel, self).__init__(x_train, y_train)
         self.genes = dict(genes)
         self.name = '-'.join(self.genes[k] for k in sorted(self.genes))
@@ -61,7 +61,7 @@ class GeneticCnnModel(GentunModel):
                                     optimizer=optimizer, momentum=momentum, reset=reset, batching=batching,
                                     batch_norm=batch_norm, verbose=verbose, nfold=nfold, pad_images=pad_images,
                                     augment=_eng.normalize_augment(augment, hw=self.input_shape[:2]),
-                                    label_smoothing=label_smoothing)
+                                    label_smoothing=label_smoothing, mix=mix)
         self.fold_parallel = fold_parallel
         self.model = self.build_model(self.genes, self.nodes, self.input_shape, self.kernels_per_layer,
                                       self.kernel_sizes, self.dense_units, self.dropout_probability, self.classes)

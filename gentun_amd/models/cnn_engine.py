@@ -117,6 +117,51 @@ def normalize_augment(augment, hw=None):
 
 
 # ---------------------------------------------------------------------------
+# The mixed step (mixup, cutmix): TrainConfig.mix
+#
+# One draw per group g and global step t mixes every real row b < nv of the batch with a partner row of the
+# same batch, images and target rows alike. key = seeds[g] ^ (fold_id * 0x632be5ab) (the dropout and
+# augmentation key), r_k = hash4(key, t, 0, 0xA0610000 + k). Integer work only: the kernels
+# (csrc/hip/cnn_mix.h), the numpy twin (utils/rng.mix_draws) and the test oracle agree to the bit.
+#   applied  nv >= 2 and (r_0 >> 8) < P24, P24 = round(prob * 2^24); otherwise the step is the unmixed step
+#   partner  o = 1 + r_1 % (nv - 1), p(b) = (b + o) % nv; rows b >= nv (a short batch's padding) are never mixed
+#   lambda   u_j = r_{16+j} >> 8, j = 0 .. 2 alpha - 2; m = the alpha-th smallest: the median of 2 alpha - 1
+#            uniforms is Beta(alpha, alpha). lam = m 2^-24, lam1 = (2^24 - m) 2^-24, exact in fp32
+#   mixup    M[b] = fp32(lam A[b]) + fp32(lam1 A[p(b)]) per element, products and sum rounded separately; A is
+#            the augmented batch (the gathered batch without augment). bf16 storage: fp32 arithmetic on the
+#            bf16 values, rounded once. The target weights are lam, lam1
+#   cutmix   cy = r_2 % Hr, cx = r_3 % Wr; bh = isqrt((Hr Hr (2^24 - m)) >> 24), bw likewise from Wr;
+#            y0 = max(cy - bh//2, 0), y1 = min(cy - bh//2 + bh, Hr), x0 / x1 likewise; M[b][i, j] = A[p(b)][i, j]
+#            inside [y0, y1) x [x0, x1), A[b][i, j] elsewhere (a select). area = (y1 - y0)(x1 - x0);
+#            lam = fp32(Hr Wr - area) * inv_hw, lam1 = fp32(area) * inv_hw, inv_hw = fp32(1) / fp32(Hr Wr)
+#   target   t[c] = fp32(lam t_b[c]) + fp32(lam1 t_p[c]), t_x the row's target under the active source
+#            ("The target row" below)
+# Everything outside the real extent of a zero-padded image stays exact zero.
+# ---------------------------------------------------------------------------
+
+def normalize_mix(mix):
+    """``None`` or ``{"kind": "mixup" | "cutmix", "alpha": 1..8, "prob": (0, 1]}`` with every key present
+    (defaults: alpha 1, prob 1.0); ``ValueError`` on anything else."""
+    if mix is None:
+        return None
+    if not isinstance(mix, dict):
+        raise ValueError("mix must be None or a dict with the keys 'kind', 'alpha' and 'prob'")
+    unknown = sorted(set(mix) - {"kind", "alpha", "prob"})
+    if unknown:
+        raise ValueError("mix: unknown keys {}".format(unknown))
+    kind, alpha, prob = mix.get("kind"), mix.get("alpha", 1), mix.get("prob", 1.0)
+    if kind not in _rng.MIX_KINDS:
+        raise ValueError("mix: kind must be 'mixup' or 'cutmix', got {!r}".format(kind))
+    if isinstance(alpha, (bool, np.bool_)) or not isinstance(alpha, (int, np.integer)) \
+            or not 1 <= alpha <= _rng.MIX_MAX_ALPHA:
+        raise ValueError("mix: alpha must be an integer from 1 to {}".format(_rng.MIX_MAX_ALPHA))
+    if isinstance(prob, (bool, np.bool_)) or not isinstance(prob, (int, float, np.integer, np.floating)) \
+            or not 0.0 < float(prob) <= 1.0 or _rng.mix_p24(prob) < 1:
+        raise ValueError("mix: prob must be a real number in (0, 1]")
+    return {"kind": str(kind), "alpha": int(alpha), "prob": float(prob)}
+
+
+# ---------------------------------------------------------------------------
 # Soft targets of the training step (label smoothing, distillation)
 #
 # The target row. For a training row with sample id ``sid`` and hard label ``y`` the target is t[0..C):
@@ -213,7 +258,8 @@ class TrainConfig(object):
     def __init__(self, epochs=(3,), learning_rate=(1e-3,), batch_size=32, dropout=0.5, loss="bce_compat",
                  dtype="fp32", seed=0, use_graph=None, eval_batch=1000, optimizer="adam", momentum=0.9,
                  reset="kernels", batching="keras", batch_norm=False, bn_momentum=0.99, bn_eps=1e-3,
-                 dp_group=None, verbose=False, nfold=None, pad_images=True, augment=None, label_smoothing=0.0):
+                 dp_group=None, verbose=False, nfold=None, pad_images=True, augment=None, label_smoothing=0.0,
+                 mix=None):
         if isinstance(epochs, int):
             epochs = (epochs,)
         if isinstance(learning_rate, (int, float)):
@@ -267,6 +313,8 @@ class TrainConfig(object):
         # optional label smoothing of the training targets (0.0: off, the hard labels); evaluation always
         # scores against the hard labels
         self.label_smoothing = normalize_label_smoothing(label_smoothing)
+        # optional mixup / cutmix of every training batch and its target rows ("The mixed step"; None: off)
+        self.mix = normalize_mix(mix)
 
     def total_epochs(self):
         return sum(self.epochs)
@@ -382,6 +430,11 @@ class FoldJob(object):
         # with the fold id, the global step and the full-batch row they fix every draw (utils/rng.aug_draws)
         self.aug = normalize_augment(getattr(cfg, "augment", None), hw=self.plan.input_shape[:2])
         self.aug_seeds = [_rng.stable_hash(self.member_seeds[c], "dropout") & 0xFFFFFFFF for c in self.gmember]
+        # mixup / cutmix (cfg.mix, "The mixed step"): the same keys
+        self.mix = normalize_mix(getattr(cfg, "mix", None))
+        if self.mix is not None and getattr(cfg, "dp_group", None) is not None:
+            raise ValueError("mix with dp_group is not supported (a row's partner can live on another rank); "
+                             "train without data parallelism or without mixup / cutmix")
         # the target table: one device tensor per job, shared by all groups (None: hard labels or smoothing)
         self.soft = None if self.soft_np is None else torch.from_numpy(self.soft_np).to(self.device)
         self.smooth_on_off = smoothing_targets(self.smooth, self.data.classes) if self.smooth > 0.0 else None
@@ -981,6 +1034,41 @@ class TorchFoldJob(FoldJob):
         out = augment_images(xb.view(Bn, G, GC // G, H, W), dy, dx, fl, (H, W))
         return out.reshape(Bn, GC, H, W)
 
+    def _mix(self, xb, yb, nv):
+        """The training batch ``xb [B, G*C, H, W]`` and its target rows ``yb [G, B, C]`` under the mix of this
+        step ("The mixed step"); ``nv [G]``: the real rows of every group's batch (host integers)."""
+        G, B = self.G, self.B
+        Bn, GC, H, W = xb.shape
+        kind = self.mix["kind"]
+        keys = np.asarray([_rng.aug_key(s, f) for s, f in zip(self.aug_seeds, self.fold_ids)], np.uint64)
+        ap, o, m, cy, cx = _rng.mix_draws(keys, self.global_step, nv, self.mix["alpha"],
+                                          _rng.mix_p24(self.mix["prob"]), (H, W))
+        rows = np.arange(B)[None, :]
+        mixed = (ap[:, None] != 0) & (rows < np.asarray(nv)[:, None])                       # [G, B]
+        perm = np.where(mixed, (rows + o[:, None]) % np.maximum(np.asarray(nv), 1)[:, None], rows)
+        lam, lam1 = np.ones(G, np.float32), np.zeros(G, np.float32)
+        box = np.zeros((G, H, W), bool)
+        for g in range(G):
+            if ap[g]:
+                bx = _rng.mix_box(cy[g], cx[g], m[g], H, W)
+                lam[g], lam1[g] = _rng.mix_weights(kind, m[g], bx, H, W)
+                box[g, bx[0]:bx[1], bx[2]:bx[3]] = True
+        dev = xb.device
+        t = lambda v: torch.from_numpy(np.ascontiguousarray(v)).to(dev)      # noqa: E731
+        mixed_t, perm_t, lam_t, lam1_t = t(mixed), t(perm), t(lam), t(lam1)
+        x5 = xb.view(Bn, G, GC // G, H, W)
+        idx = perm_t.t()[:, :, None, None, None].expand_as(x5)
+        part = torch.gather(x5, 0, idx)
+        sel = mixed_t.t()[:, :, None, None, None]
+        if kind == "mixup":
+            new = x5 * lam_t.view(1, G, 1, 1, 1) + part * lam1_t.view(1, G, 1, 1, 1)
+        else:
+            new, sel = part, sel & t(box)[None, :, None, :, :]
+        xb = torch.where(sel, new, x5).reshape(Bn, GC, H, W)
+        yp = torch.gather(yb, 1, perm_t[:, :, None].expand_as(yb))
+        ym = yb * lam_t.view(G, 1, 1) + yp * lam1_t.view(G, 1, 1)
+        return xb, torch.where(mixed_t[:, :, None], ym, yb)
+
     def _dp(self):
         """(group, rank, world, first row, end row) of the data-parallel slice."""
         grp = self.cfg.dp_group
@@ -1012,6 +1100,7 @@ class TorchFoldJob(FoldJob):
         dp = self._dp()
         idx = self.epoch_idx.index_select(0, self.step_ctr).view(self.G, self.B)
         nval = self.epoch_valid.index_select(0, self.step_ctr).view(self.G, 1).float()
+        nv_host = nval.view(-1).to(torch.int64).cpu().numpy() if self.mix is not None else None
         self.step_ctr.add_(1)
         rows = torch.arange(self.B, device=self.device)[None, :].float()
         wt = (rows < nval).float() / nval.clamp_min(1.0)
@@ -1022,6 +1111,8 @@ class TorchFoldJob(FoldJob):
         if self.aug is not None:
             xb = self._augment(xb, dp[3] if dp is not None else 0)
         yb = self._train_targets().index_select(0, idx.reshape(-1)).view(self.G, idx.shape[1], -1)
+        if self.mix is not None:
+            xb, yb = self._mix(xb, yb, nv_host)
         self.flat.grad.zero_()
         if self.amp:
             with torch.autocast(device_type="cuda", dtype=torch.bfloat16):

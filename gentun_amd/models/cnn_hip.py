@@ -16,7 +16,7 @@ population size and each launch is ``Q`` times larger -- the size at which
 
 Step (one HIP graph, replayed epochs x steps times):
 
-  step_begin -> [cfg.augment: gt_augment writes the shifted / flipped batch] ->
+  step_begin -> [cfg.augment: gt_augment writes the shifted / flipped batch; cfg.mix: gt_augment_mix] ->
   per stage: conv IN (first stage gathers the batch from the device-resident
   dataset, or reads the augmented batch), conv N_0..N_{K-1} (only groups whose node is
   active; fused N-ary Add of the node's predecessors), conv OUT (groups
@@ -584,9 +584,9 @@ class HipPopJob(FoldJob):
         kernels run): ``in[0]`` is the augmented batch and the table is the constant ``g * B + b``.
         ``self.fwd_ops`` stays the dataset-reading list the evaluation launches are copied from. Off
         (None): nothing is allocated and the training launches ARE ``self.fwd_ops``."""
-        self.aug_args = self.aug_x = self.aug_table = None
+        self.aug_args = self.mix_args = self.aug_x = self.aug_table = None
         self.train_fwd_ops = self.fwd_ops
-        if self.aug is None:
+        if self.aug is None and self.mix is None:
             return
         Q, B, dev = self.Q, self.B, self.device
         h0r, w0r, c0 = self.plan.input_shape
@@ -594,14 +594,23 @@ class HipPopJob(FoldJob):
         self.aug_x = torch.zeros((Q * B, hp, wp, pad8(c0)), dtype=self.adt, device=dev)
         self.aug_table = torch.arange(Q * B, dtype=torch.int64, device=dev).view(1, Q, B).repeat(
             self.steps_per_epoch, 1, 1).contiguous()
-        a = K.AugArgs()
+        # cfg.mix ("The mixed step", cnn_engine.py): gt_augment_mix (csrc/hip/cnn_mix.hip) fills the batch
+        # instead, augmentation and mixing in one pass; shift 0 / flip 0 without cfg.augment
+        a = K.AugArgs() if self.mix is None else K.MixArgs()
         a.src, a.out = self.data.x.data_ptr(), self.aug_x.data_ptr()
         a.gather, a.st = self.epoch_idx.data_ptr(), self.state.data_ptr()
         a.fold_ids, a.seeds = self.fold_ids_t.data_ptr(), self.drop_seeds_t.data_ptr()
-        a.row_off = 0                     # data parallelism with augmentation is refused (_setup_dp)
         a.Q, a.B, a.Hp, a.Wp, a.Hr, a.Wr, a.Cp = Q, B, hp, wp, h0r, w0r, pad8(c0)
-        a.shift, a.flip, a.prec = self.aug["shift"], 1 if self.aug["flip"] else 0, self.prec
-        self.aug_args = a
+        aug = self.aug or {"shift": 0, "flip": False}
+        a.shift, a.flip, a.prec = aug["shift"], 1 if aug["flip"] else 0, self.prec
+        if self.mix is None:
+            a.row_off = 0                 # data parallelism with augmentation is refused (_setup_dp)
+            self.aug_args = a
+        else:
+            a.valid = self.epoch_valid.data_ptr()
+            a.kind, a.alpha = _rng.MIX_KINDS[self.mix["kind"]], self.mix["alpha"]
+            a.p24 = _rng.mix_p24(self.mix["prob"])
+            self.mix_args = a
         ops = []
         for kind, c, Lr in self.fwd_ops:
             if kind == "conv" and c.gather:
@@ -688,6 +697,21 @@ class HipPopJob(FoldJob):
             else:
                 hs.soft, hs.t_on, hs.t_off = 0, float(self.smooth_on_off[0]), float(self.smooth_on_off[1])
             self.head_soft_args = hs
+        # mixup / cutmix: gt_head_mix recomputes the step's draw and mixes the two rows' targets (hard labels
+        # are t_on = 1, t_off = 0). Off: nothing is built.
+        self.head_mix_args = None
+        if self.mix is not None:
+            hm = K.HeadMixArgs()
+            if self.head_soft_args is not None:
+                hm.soft = self.head_soft_args            # by value
+            else:
+                hm.soft.head, hm.soft.soft, hm.soft.t_on, hm.soft.t_off = hd, 0, 1.0, 0.0
+            hm.fold_ids, hm.seeds = self.fold_ids_t.data_ptr(), self.drop_seeds_t.data_ptr()
+            hm.kind, hm.alpha = _rng.MIX_KINDS[self.mix["kind"]], self.mix["alpha"]
+            hm.p24 = _rng.mix_p24(self.mix["prob"])
+            hm.Hr, hm.Wr = self.plan.input_shape[:2]
+            hm.inv_hw = float(np.float32(1.0) / np.float32(hm.Hr * hm.Wr))
+            self.head_mix_args = hm
         dd = K.DenseDgradArgs()
         dd.dH, dd.wt, dd.dx = self.dH.data_ptr(), 0, self.grad[self.last].data_ptr()
         dd.dHp = self.dHp.data_ptr()
@@ -758,7 +782,7 @@ class HipPopJob(FoldJob):
                 for i, n in enumerate(wslots):
                     wa.inp[i] = self._slot_ptr(n)
                 wa.gather = gather_train if first else 0
-                if first and self.aug_args is not None:      # the augmented batch through its constant table
+                if first and self.aug_x is not None:         # the augmented / mixed batch through its constant table
                     wa.inp[0], wa.gather = self.aug_x.data_ptr(), self.aug_table.data_ptr()
                 wa.st = self.state.data_ptr()
                 wa.dz = self.grad[L.name].data_ptr()
@@ -982,9 +1006,13 @@ class HipPopJob(FoldJob):
         plan = [("k", "gt_step_begin", (self.state.data_ptr(),), main, "step_begin")]
         if self.aug_args is not None:
             plan.append(("k", "gt_augment", (self.aug_args,), main, "augment"))
+        if self.mix_args is not None:
+            plan.append(("k", "gt_augment_mix", (self.mix_args,), main, "augment_mix"))
         plan += self._fwd_plan(self.train_fwd_ops)
         head = ("k", "gt_head", (self.head_args,), main, "head") if self.head_soft_args is None else \
             ("k", "gt_head_soft", (self.head_soft_args,), main, "head_soft")
+        if self.head_mix_args is not None:
+            head = ("k", "gt_head_mix", (self.head_mix_args,), main, "head_mix")
         plan += [("k", "gt_dense_fwd", (self.dense_fwd_args,), main, "dense_fwd"), head,
                  ("k", "gt_dense_dgrad", (self.dense_dgrad_args,), main, "dense_dgrad")]   # reads W1 before its update
         side2 = self.side2

@@ -164,6 +164,13 @@ class HeadSoftArgs(C.Structure):
     _fields_ = [("head", HeadArgs), ("soft", P), ("t_on", C.c_float), ("t_off", C.c_float)]
 
 
+class HeadMixArgs(C.Structure):
+    """csrc/hip/cnn_dense.hip HeadMixArgs: the training head of a mixup / cutmix step (gt_head_mix) --
+    HeadSoftArgs by value, then the key material and the settings of the step's draw (csrc/hip/cnn_mix.h)."""
+    _fields_ = [("soft", HeadSoftArgs), ("fold_ids", P), ("seeds", P), ("seed", C.c_uint), ("kind", I),
+                ("alpha", I), ("p24", C.c_uint), ("Hr", I), ("Wr", I), ("inv_hw", C.c_float)]
+
+
 class HeadPredictArgs(C.Structure):
     """csrc/hip/cnn_dense.hip HeadPredictArgs: logits and probabilities of every row (gt_head_predict)."""
     _fields_ = [("plog", P), ("b2", P), ("logits", P), ("proba", P), ("G", I), ("B", I), ("Up", I), ("C", I)]
@@ -385,7 +392,7 @@ PROG_OPS = {"record": 0, "wait": 1, "gt_step_begin": 2, "gt_conv_fwd": 3, "gt_co
             "gt_wgrad_reduce": 5, "gt_bn_fwd": 6, "gt_bn_bwd": 7, "gt_dense_fwd": 8, "gt_head": 9,
             "gt_dense_dgrad": 10, "gt_dense_wgrad_adam": 11, "gt_adam_segments": 12, "gt_pool_fwd": 13,
             "gt_pool_fwd_mask": 14, "gt_pool_bwd_mask": 15, "gt_wino_wtrans": 16,
-            "gt_conv_wfrag": 17, "gt_head_soft": 18, "gt_augment": 19}
+            "gt_conv_wfrag": 17, "gt_head_soft": 18, "gt_head_mix": 19, "gt_augment_mix": 20, "gt_augment": 21}
 
 
 class AugArgs(C.Structure):
@@ -393,6 +400,14 @@ class AugArgs(C.Structure):
     _fields_ = [("src", P), ("out", P), ("gather", P), ("st", P), ("fold_ids", P), ("seeds", P),
                 ("seed", C.c_uint), ("row_off", I), ("Q", I), ("B", I), ("Hp", I), ("Wp", I), ("Hr", I), ("Wr", I),
                 ("Cp", I), ("shift", I), ("flip", I), ("prec", I)]
+
+
+class MixArgs(C.Structure):
+    """csrc/hip/cnn_mix.hip MixArgs: mixup / cutmix of the training batch, fused with its augmentation
+    (gt_augment_mix)."""
+    _fields_ = [("src", P), ("out", P), ("gather", P), ("valid", P), ("st", P), ("fold_ids", P), ("seeds", P),
+                ("seed", C.c_uint), ("Q", I), ("B", I), ("Hp", I), ("Wp", I), ("Hr", I), ("Wr", I), ("Cp", I),
+                ("shift", I), ("flip", I), ("prec", I), ("kind", I), ("alpha", I), ("p24", C.c_uint)]
 
 
 class InitSeg(C.Structure):
@@ -429,6 +444,13 @@ def lib():
         L.gt_head_soft.restype = I
         L.gt_sizeof_head_soft_args.restype = C.c_size_t
         assert L.gt_sizeof_head_soft_args() == C.sizeof(HeadSoftArgs), "HeadSoftArgs ABI mismatch"
+        for fname, sname, st in (("gt_head_mix", "head_mix", HeadMixArgs), ("gt_augment_mix", "mix", MixArgs)):
+            fn = getattr(L, fname)
+            fn.argtypes = [C.POINTER(st), P]
+            fn.restype = I
+            size = getattr(L, "gt_sizeof_{}_args".format(sname))
+            size.restype = C.c_size_t
+            assert size() == C.sizeof(st), st.__name__ + " ABI mismatch"
         L.gt_head_predict.argtypes = [C.POINTER(HeadPredictArgs), P]
         L.gt_head_predict.restype = I
         L.gt_sizeof_head_predict_args.restype = C.c_size_t

@@ -236,7 +236,8 @@ def _settings_key(model):
             getattr(c, "reset", None), getattr(c, "batching", None), getattr(c, "batch_norm", None),
             model.nodes, model.input_shape, model.kernels_per_layer, model.kernel_sizes, model.dense_units,
             model.classes, tuple(sorted((getattr(c, "augment", None) or {}).items())),
-            float(getattr(c, "label_smoothing", 0.0) or 0.0))
+            float(getattr(c, "label_smoothing", 0.0) or 0.0),
+            tuple(sorted((getattr(c, "mix", None) or {}).items())))
 
 
 def _check_shared_settings(chunk):

@@ -102,7 +102,62 @@ def aug_draws(key, step, rows, shift, flip):
     return dy, dx, fl
 
 
-MC_KEY = 0x4D434452         # hash4 counter of the Monte-Carlo dropout member key ("MCDR")
+MIX_CTR = 0xA0610000        # hash4 counters of the mixup / cutmix draws (models/cnn_engine.py "The mixed step")
+MIX_KINDS = {"mixup": 0, "cutmix": 1}
+MIX_MAX_ALPHA = 8
+_ONE24 = 1 << 24
+
+
+def mix_p24(prob):
+    """``round(prob * 2^24)``: a step is mixed iff its 24-bit draw is below this."""
+    return int(round(float(prob) * _ONE24))
+
+
+def mix_box(cy, cx, m, hr, wr):
+    """``(y0, y1, x0, x1)`` of the cutmix box centred at ``(cy, cx)`` under the 24-bit draw ``m``: sides
+    ``isqrt((Hr Hr (2^24 - m)) >> 24)`` and likewise for ``Wr``, clipped to the image. Python integers."""
+    import math
+    cy, cx, m, hr, wr = int(cy), int(cx), int(m), int(hr), int(wr)
+    bh = math.isqrt((hr * hr * (_ONE24 - m)) >> 24)
+    bw = math.isqrt((wr * wr * (_ONE24 - m)) >> 24)
+    ty, tx = cy - bh // 2, cx - bw // 2
+    return max(ty, 0), min(ty + bh, hr), max(tx, 0), min(tx + bw, wr)
+
+
+def mix_weights(kind, m, box, hr, wr):
+    """``(lam, lam1)`` as numpy fp32: the weights of a row and of its partner in the mixed target (and, for
+    mixup, in the mixed image). mixup: ``m 2^-24`` and ``(2^24 - m) 2^-24``, both exact; cutmix: the kept and
+    the pasted share of the area, ``fp32(Hr Wr - area) * inv_hw`` and ``fp32(area) * inv_hw`` with
+    ``inv_hw = fp32(1) / fp32(Hr Wr)``."""
+    import numpy as np
+    if kind == "mixup":
+        s = np.float32(2.0 ** -24)
+        return np.float32(int(m)) * s, np.float32(_ONE24 - int(m)) * s
+    y0, y1, x0, x1 = box
+    area, hw = (y1 - y0) * (x1 - x0), int(hr) * int(wr)
+    inv_hw = np.float32(np.float32(1.0) / np.float32(hw))
+    return np.float32(np.float32(hw - area) * inv_hw), np.float32(np.float32(area) * inv_hw)
+
+
+def mix_draws(key, step, nv, alpha, p24, hw):
+    """The mixup / cutmix draw of global step ``step`` under ``key`` (:func:`aug_key`) for batches of ``nv``
+    real rows; ``key`` / ``step`` / ``nv`` broadcast. Returns int64 arrays ``(applied, o, m, cy, cx)``:
+    whether the step is mixed, the partner offset (``p(b) = (b + o) % nv``), the 24-bit median of
+    ``2 alpha - 1`` uniforms (Beta(alpha, alpha) * 2^24) and the cutmix centre in the real image ``hw``.
+    ``o`` and ``m`` are 0 where the step is not mixed."""
+    import numpy as np
+    key, step, nv = np.broadcast_arrays(_u32(key), _u32(step), np.asarray(nv, np.int64))
+    r = [hash4(key, step, 0, MIX_CTR + k) for k in range(4)]
+    applied = (nv >= 2) & ((r[0] >> np.uint64(8)) < np.uint64(int(p24)))
+    o = np.where(applied, 1 + (r[1] % np.maximum(nv - 1, 1).astype(np.uint64)).astype(np.int64), 0)
+    u = np.stack([hash4(key, step, 0, MIX_CTR + 16 + j) >> np.uint64(8) for j in range(2 * int(alpha) - 1)])
+    m = np.where(applied, np.sort(u, axis=0)[int(alpha) - 1].astype(np.int64), 0)
+    cy = (r[2] % np.uint64(int(hw[0]))).astype(np.int64)
+    cx = (r[3] % np.uint64(int(hw[1]))).astype(np.int64)
+    return applied.astype(np.int64), o, m, cy, cx
+
+
+MC_KEY = 0x4D434452        # hash4 counter of the Monte-Carlo dropout member key ("MCDR")
 
 
 def mc_threshold(dropout):

@@ -18,6 +18,7 @@
 #   bash tools/gpu.sh cnn-predict             CnnClassifier.predict: HIP predictor at 32 / 256 rows per launch vs stock torch on the GPU (ROWS= REPS=)
 #   bash tools/gpu.sh cnn-ensemble            CnnEnsemble.predict: one k-group launch set vs k predictors one by one vs stock torch; fit_ensemble vs k fits (ROWS= REPS= K= FIT_ROWS=)
 #   bash tools/gpu.sh cnn-augment             TrainConfig.augment: step time off / on (and the parent tree in ab_old/), gt_augment's kernel time (GROUPS_LIST= REPS= PROF_GROUPS= OUT=)
+#   bash tools/gpu.sh cnn-mix                 TrainConfig.mix: step time off / augment / mixup / cutmix / both (and the parent tree in ab_old/), the kernels' time from kernel trace runs of their own, the accuracy record (GROUPS_LIST= REPS= PROF_GROUPS= OUT= ACC=0)
 #   bash tools/gpu.sh cnn-distill             soft targets: step time of the parent tree (ab_old/) / off / label_smoothing / a target table, the head kernels' time from a kernel trace run of its own, the distillation record (GROUPS_LIST= REPS= PROF_GROUPS= OUT= ACC=0)
 #   bash tools/gpu.sh cnn-tta                 predict(tta=...): views and mean on the device vs V plain HIP predicts combined in numpy vs stock torch, classifier and k-ensemble (ROWS= FIT_ROWS= K= REPS= OUT=)
 #   bash tools/gpu.sh cnn-occlusion           occlusion(): copies built and packed on the device vs occlusion_views in numpy + plain HIP predicts vs stock torch, classifier and k-ensemble (ROWS= FIT_ROWS= K= REPS= OUT= TIME=)
@@ -190,6 +191,26 @@ cnn-augment)
   grep -E "Name|augment" $out/kernel_stats.csv | cut -c1-300; rc=$?
   [ $rc -eq 0 ] || tail -5 $out/bench.err $out/prof.log 2>/dev/null
   exit $rc ;;
+cnn-mix)
+  # step time of every variant (and in ab_old/, the built parent tree, when it is there), then gt_augment,
+  # gt_augment_mix and the head kernels from one kernel trace per child, each step under its own time limit,
+  # then the accuracy record; files are kept under $OUT
+  out=${OUT:-/tmp/cnn_mix}; heartbeat; mkdir -p $out; rocprof_env
+  parent=""; [ -d ab_old/gentun_amd/_native ] && parent="--parent ab_old"
+  timeout -k 10 ${TIME:-1000} python -u tools/bench_cnn_mix.py --groups ${GROUPS_LIST:-25,80} --reps ${REPS:-5} $parent \
+    > $out/bench.json 2> $out/bench.err &&
+  cut -c1-6000 $out/bench.json || { tail -5 $out/bench.err; exit 1; }
+  for v in aug aug+mixup aug+cutmix smooth; do
+    rm -rf /tmp/prof_mix
+    timeout -k 10 200 rocprofv3 --kernel-trace --stats -d /tmp/prof_mix -o run --output-format csv -- \
+      python3 tools/bench_cnn_mix.py --child .:${PROF_GROUPS:-25}:$v > $out/prof_$v.log 2>&1 \
+      || { tail -5 $out/prof_$v.log; exit 1; }
+    find /tmp/prof_mix -name "*kernel_stats.csv" -exec cp {} $out/kernel_stats_$v.csv \;
+    echo "== $v"; grep -E "Name|augment|head_fwd" $out/kernel_stats_$v.csv | cut -c1-300
+  done
+  [ "${ACC:-1}" = 0 ] || { timeout -k 10 ${ACC_TIME:-300} python -u tools/bench_cnn_mix.py --accuracy \
+    > $out/accuracy.json 2> $out/accuracy.err && cut -c1-2000 $out/accuracy.json || { tail -5 $out/accuracy.err; exit 1; }; }
+  exit 0 ;;
 cnn-distill)
   # step time on hard labels / smoothed labels / a target table (and in ab_old/, the built parent tree, when it is
   # there), then the head kernels' own time from a kernel trace of one child run of its own, then the
