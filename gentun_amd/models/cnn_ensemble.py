@@ -28,7 +28,8 @@ from .cnn_fitted import (CnnClassifier, TtaState, cam_check, cam_check_hip, cam_
                          mc_check_hip, mc_result, mc_state, mc_statistics, occlusion_by_views, occlusion_fill,
                          occlusion_grid, occlusion_state, occlusion_targets, predict_batch, rise_by_views,
                          rise_check, rise_check_hip, rise_state, saliency_check,
-                         saliency_check_hip, saliency_info, saliency_reduce, saliency_state, tta_views)
+                         saliency_check_hip, saliency_info, saliency_reduce, saliency_state, smooth_spec,
+                         tta_views)
 
 FORMAT = "gentun-cnn-ensemble/1"
 OUTPUTS = ("proba", "label", "votes", "vote_label", "member_proba", "member_logits")
@@ -303,14 +304,16 @@ class CnnEnsemble(object):
         return (cam, {"target": res[1], "base": res[2]}) if return_info else cam
 
     def saliency(self, x, target=None, score="logit", method="gradient", steps=16, baseline=0.0, reduce="absmax",
-                 device=None, batch=256, backend=None, return_info=False):
+                 device=None, batch=256, backend=None, return_info=False, smooth=None):
         """Input-gradient saliency of the ensemble (``CnnClassifier.saliency``): the weighted mean, in member
         order with :func:`combine_maps`' rounding, of the members' signed attributions ``a`` (before ``reduce``),
         every member under its own score of the ensemble's target (``None``: the first maximum of the combined
         probabilities). With ``score="proba"`` this is exactly the attribution of the combined probability (the
         gradient is linear in the score); with ``"logit"`` it is that of the weighted mean of the members' logits.
-        ``info["base"]`` and ``info["baseline_score"]`` are the weighted means of the members' scores."""
-        steps, x0 = saliency_check(score, method, steps, baseline, reduce, batch, self.input_shape[2])
+        ``info["base"]`` and ``info["baseline_score"]`` are the weighted means of the members' scores. ``smooth``
+        (``CnnClassifier.saliency``): every member's noise-averaged map at the same noisy points, then combined."""
+        steps, x0 = saliency_check(score, method, steps, baseline, reduce, batch, self.input_shape[2], smooth)
+        smooth = smooth_spec(smooth, method)
         x = self.members[0]._check_x(x)
         target = occlusion_targets(target, x.shape[0], self.classes, "saliency")
         dev = torch.device("cpu" if device is None else device)
@@ -319,13 +322,13 @@ class CnnEnsemble(object):
         if backend == "hip":
             saliency_check_hip(self.classes, steps, method, 256)         # the class limit, before a predictor exists
             pred = self.hip_predictor(dev, batch)
-            saliency_check_hip(self.classes, steps, method, pred.EB)
-            res = pred.saliency(x, target, score, method, steps, x0, reduce)
+            saliency_check_hip(self.classes, steps, method, pred.EB, smooth)
+            res = pred.saliency(x, target, score, method, steps, x0, reduce, smooth)
         elif backend == "torch":
             if target is None:
                 member = np.stack([m._torch_predict(x, dev, int(batch), torch.float32)[1] for m in self.members])
                 target = np.argmax(combine(member, self.weights)[0], axis=1).astype(np.int64)
-            per = [m._torch_saliency(x, target, score, method, steps, x0, dev, int(batch), torch.float32)
+            per = [m._torch_saliency(x, target, score, method, steps, x0, dev, int(batch), torch.float32, smooth)
                    for m in self.members]
             res = (saliency_reduce(combine_maps([p[0] for p in per], self.weights), reduce), target,
                    combine_maps([p[2] for p in per], self.weights),
@@ -496,10 +499,11 @@ class HipEnsemblePredictor(object):
         their weights."""
         return gradcam_state(self, score, relu, self.k, self.weight).run(self, x, target)
 
-    def saliency(self, x, target, score, method, steps, x0, reduce):
+    def saliency(self, x, target, score, method, steps, x0, reduce, smooth=None):
         """``(map, target, base, baseline_score)`` of validated arguments (``CnnEnsemble.saliency``) over the
         ``k`` members and their weights."""
-        return saliency_state(self, self.k, self.weight).run(self, x, target, score, method, steps, x0, reduce)
+        return saliency_state(self, self.k, self.weight).run(self, x, target, score, method, steps, x0, reduce,
+                                                             smooth)
 
     def predict_mc(self, x, samples, dropout, seed, return_samples):
         """The dict of validated arguments (``CnnEnsemble.predict_mc``) over the ``k`` members and their

@@ -22,7 +22,7 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
-from ..ops.cnn_kernels import IG_MAX_STEPS
+from ..ops.cnn_kernels import IG_MAX_STEPS, SG_METHODS, SG_STATS
 from .genome import ConvSpec, make_plan
 
 FORMAT = "gentun-cnn/1"
@@ -340,9 +340,35 @@ SAL_REDUCE = ("absmax", "sum", None)
 SAL_MAX_STEPS = IG_MAX_STEPS     # one constant: cnn_kernels checks it against the library's IG_MAXM
 
 
-def saliency_check(score, method, steps, baseline, reduce, batch, channels):
-    """The validated ``(steps, baseline fp32 [channels])`` of a saliency request; ``ValueError`` on a bad option,
-    before any work."""
+SG_DEFAULTS = {"samples": 32, "noise": 0.15, "seed": 0, "stat": "mean"}
+
+
+def smooth_spec(smooth, method="gradient"):
+    """The validated ``(samples, noise fp32, seed, stat)`` of a ``smooth=`` request (missing keys take
+    ``SG_DEFAULTS``), or None for ``smooth=None``; ``ValueError`` on anything else."""
+    if smooth is None:
+        return None
+    if not isinstance(smooth, dict) or set(smooth) - set(SG_DEFAULTS):
+        raise ValueError("smooth {!r}: expected None or a dict with keys from {}".format(smooth, sorted(SG_DEFAULTS)))
+    if method == "integrated":
+        raise ValueError("saliency: smooth= does not combine with method='integrated'")
+    o = dict(SG_DEFAULTS, **smooth)
+    if not _is_int(o["samples"]) or not 1 <= int(o["samples"]) <= SAL_MAX_STEPS:
+        raise ValueError("smooth: samples must be an integer in [1, {}], got {!r}".format(SAL_MAX_STEPS, o["samples"]))
+    nz = o["noise"]
+    if isinstance(nz, (bool, np.bool_)) or not isinstance(nz, (int, float, np.integer, np.floating)) \
+            or not np.isfinite(nz) or not 0 <= nz <= 1:
+        raise ValueError("smooth: noise must be a finite number in [0, 1], got {!r}".format(nz))
+    if not _is_int(o["seed"]) or not 0 <= int(o["seed"]) < 2 ** 32:
+        raise ValueError("smooth: seed must be an integer in [0, 2^32), got {!r}".format(o["seed"]))
+    if not (isinstance(o["stat"], str) and o["stat"] in SG_STATS):
+        raise ValueError("smooth: stat {!r}: expected one of {}".format(o["stat"], SG_STATS))
+    return int(o["samples"]), np.float32(nz), int(o["seed"]), o["stat"]
+
+
+def saliency_check(score, method, steps, baseline, reduce, batch, channels, smooth=None):
+    """The validated ``(steps, baseline fp32 [channels])`` of a saliency request; ``ValueError`` on a bad option
+    (``smooth`` included: :func:`smooth_spec`), before any work."""
     if score not in CAM_SCORES:
         raise ValueError("score {!r}: expected one of {}".format(score, CAM_SCORES))
     if method not in SAL_METHODS:
@@ -353,6 +379,7 @@ def saliency_check(score, method, steps, baseline, reduce, batch, channels):
         raise ValueError("saliency: steps must be an integer in [1, {}], got {!r}".format(SAL_MAX_STEPS, steps))
     if not _is_int(batch) or int(batch) < 1:
         raise ValueError("batch must be a positive integer")
+    smooth_spec(smooth, method)
     try:
         base = occlusion_fill(baseline, channels)
     except ValueError:
@@ -388,6 +415,41 @@ def saliency_finish(grads, x, x0, method):
     return (xs - x0.astype(acc.dtype)) * (acc * (ft(1) / ft(len(grads))))
 
 
+def smooth_sigma(x, noise):
+    """fp32 ``[n]``: ``fp32(noise) * (max - min)`` of every image of ``x`` ``[n, H, W, C]``, in fp32."""
+    xs = x.astype(np.float32, copy=False)
+    return np.float32(noise) * (xs.max(axis=(1, 2, 3)) - xs.min(axis=(1, 2, 3)))
+
+
+def smooth_point(x, sigma, seed, k, n0=0):
+    """Sample ``k`` of every image of ``x`` ``[n, H, W, C]`` (images ``n0 ..`` of the call) in the dtype of ``x``:
+    ``x + sigma_n * z`` with ``z`` of :func:`gentun_amd.utils.rng.sg_noise``. fp32: ``sigma_n * z`` is rounded to
+    fp32, then the sum (``gt_sg_points``); fp64 stays fp64."""
+    from ..utils.rng import sg_noise
+    n, h, w, c = x.shape
+    z = sg_noise(seed, n0 + np.arange(n), [k], h, w, c)[:, 0]
+    return x + (sigma.astype(np.float64).reshape(-1, 1, 1, 1) * z).astype(x.dtype)
+
+
+def smooth_finish(grads, x, method, stat):
+    """The signed attribution ``[n, H, W, C]`` of the gradients ``grads`` at the noisy points (a list in ascending
+    sample order) in their dtype, as ``gt_sg_reduce`` forms it: the ordered sums ``s1`` of ``g`` and ``s2`` of
+    ``g * g``, ``mean = s1 * (1 / S)`` and ``msq = s2 * (1 / S)`` with ``1 / S`` rounded first; ``"mean"``: the mean,
+    ``"sq"``: ``msq``, ``"var"``: ``max(msq - mean * mean, 0)``; ``"gradxinput"`` multiplies by the clean ``x``
+    (``"mean"``) or by ``x * x``."""
+    ft = grads[0].dtype.type
+    s1, s2 = grads[0], grads[0] * grads[0]
+    for g in grads[1:]:
+        s1, s2 = s1 + g, s2 + g * g
+    inv = ft(1) / ft(len(grads))
+    mean, msq = s1 * inv, s2 * inv
+    a = mean if stat == "mean" else msq if stat == "sq" else np.maximum(msq - mean * mean, ft(0))
+    if method == "gradient":
+        return a
+    xs = x.astype(a.dtype)
+    return a * xs if stat == "mean" else a * (xs * xs)
+
+
 def saliency_reduce(a, reduce):
     """The channel reduction of a signed attribution ``[n, H, W, C]``: ``"absmax"`` ``max_c |a|``, ``"sum"`` the
     channels added in order, ``None`` the array itself."""
@@ -401,12 +463,14 @@ def saliency_reduce(a, reduce):
     return acc
 
 
-def saliency_check_hip(classes, steps, method, EB):
+def saliency_check_hip(classes, steps, method, EB, smooth=None):
     """The ``ValueError`` of what the HIP saliency path does not take, before its state is built."""
     if classes > 16:
         raise ValueError("HIP head kernel supports at most 16 classes")
     if method == "integrated" and steps > EB:
         raise ValueError("saliency: {} steps do not fit {} rows per launch".format(steps, EB))
+    if smooth is not None and smooth[0] > EB:
+        raise ValueError("saliency: {} smooth samples do not fit {} rows per launch".format(smooth[0], EB))
 
 
 def occlusion_by_views(scores, x, target, patch, stride, fill, batch, rows=4096):
@@ -834,7 +898,7 @@ class CnnClassifier(object):
         return (cam, {"target": res[1], "base": res[2]}) if return_info else cam
 
     def saliency(self, x, target=None, score="logit", method="gradient", steps=16, baseline=0.0, reduce="absmax",
-                 device=None, batch=256, backend=None, return_info=False):
+                 device=None, batch=256, backend=None, return_info=False, smooth=None):
         """Per-pixel attribution of ``x`` ``[n, H, W, C]`` (or one image) at input resolution, fp32. With ``s`` the
         logit (``score="logit"``) or the probability (``"proba"``) of the target class (``None``: the model's own
         label, one class index, or one per image -- :meth:`gradcam`'s definitions) and ``g = ds/dx``:
@@ -849,22 +913,32 @@ class CnnClassifier(object):
         with ``base = s(x)``; for ``"integrated"`` also ``"baseline_score"``, ``s(x0)`` per row, so that
         ``a.sum() ~ base - baseline_score`` (completeness).
 
+        ``smooth={"samples": S, "noise": f, "seed": s, "stat": "mean" | "sq" | "var"}`` (``"gradient"`` and
+        ``"gradxinput"`` only; missing keys: 32, 0.15, 0, ``"mean"``) replaces ``g(x)`` by a statistic of the
+        gradients at ``S <= 64`` noisy copies ``x + sigma_n z`` with ``sigma_n = f * (max - min)`` of image ``n``
+        and ``z`` standard normal, keyed by ``(seed, index of the image in the call, sample, pixel, channel)``
+        (:func:`gentun_amd.utils.rng.sg_noise`): the mean (SmoothGrad, Smilkov et al.), the mean of squares
+        (SmoothGrad^2) or the variance (VarGrad, Adebayo et al.), formed by :func:`smooth_finish`;
+        ``"gradxinput"`` multiplies by the clean ``x`` (``x * x`` for ``"sq"`` and ``"var"``). Target and ``base``
+        are those of the clean image.
+
         ``device`` / ``backend`` / ``batch`` as in :meth:`predict`: the CPU or ``backend="torch"`` runs the
         stock-torch forward under autograd on the input; a ``cuda`` device runs the HIP predictor's forward with the
         pool masks on, then the training step's own data-gradient launches in evaluation mode down to
         ``gt_conv_in_dgrad`` (:class:`SaliencyState`)."""
-        steps, x0 = saliency_check(score, method, steps, baseline, reduce, batch, self.input_shape[2])
+        steps, x0 = saliency_check(score, method, steps, baseline, reduce, batch, self.input_shape[2], smooth)
+        smooth = smooth_spec(smooth, method)
         x = self._check_x(x)
         target = occlusion_targets(target, x.shape[0], self.classes, "saliency")
         dev = torch.device("cpu" if device is None else device)
         if backend is None:
             backend = "hip" if dev.type == "cuda" else "torch"
         if backend == "hip":
-            saliency_check_hip(self.classes, steps, method, predict_batch(batch))
-            res = self.hip_predictor(dev, batch).saliency(x, target, score, method, steps, x0, reduce)
+            saliency_check_hip(self.classes, steps, method, predict_batch(batch), smooth)
+            res = self.hip_predictor(dev, batch).saliency(x, target, score, method, steps, x0, reduce, smooth)
         elif backend == "torch":
             a, tgt, base, bs = self._torch_saliency(x, target, score, method, steps, x0, dev, int(batch),
-                                                    torch.float32)
+                                                    torch.float32, smooth)
             res = (saliency_reduce(a, reduce), tgt, base, bs)
         else:
             raise ValueError("unknown backend {!r}".format(backend))
@@ -900,14 +974,22 @@ class CnnClassifier(object):
             tgt[s:s + m] = t
         return grad, tgt, base
 
-    def _torch_saliency(self, x, target, score, method, steps, x0, dev, batch, dtype):
+    def _torch_saliency(self, x, target, score, method, steps, x0, dev, batch, dtype, smooth=None):
         """``(a [n, H, W, C] signed, target int64 [n], base [n], baseline_score [n] or None)`` by stock torch in
         ``dtype`` (fp32, or fp64: the tests' reference, which also forms the interpolation points and the sums in
         fp64): :meth:`_torch_input_grad` at ``x`` -- or, for ``"integrated"``, at every point of
-        :func:`ig_point` for the target and ``base`` of ``x`` itself -- finished by :func:`saliency_finish`."""
+        :func:`ig_point` for the target and ``base`` of ``x`` itself -- finished by :func:`saliency_finish`. With
+        ``smooth`` (:func:`smooth_spec`'s tuple): the gradients at the points of :func:`smooth_point` for the
+        target of ``x`` itself, finished by :func:`smooth_finish`."""
         ftype = np.float64 if dtype == torch.float64 else np.float32
         xs = x.astype(ftype)
         g, tgt, base = self._torch_input_grad(xs, target, score, dev, batch, dtype)
+        if smooth is not None:
+            S, noise, seed, stat = smooth
+            sigma = smooth_sigma(x, noise)
+            grads = [self._torch_input_grad(smooth_point(xs, sigma, seed, k), tgt, score, dev, batch, dtype)[0]
+                     for k in range(S)]
+            return smooth_finish(grads, xs, method, stat), tgt, base, None
         if method != "integrated":
             return saliency_finish([g], xs, x0, method), tgt, base, None
         grads = [self._torch_input_grad(ig_point(xs, x0, al), tgt, score, dev, batch, dtype)[0]
@@ -1763,6 +1845,17 @@ class SaliencyState(object):
         p.raw, p.out, p.x0, p.rows = self.raw.data_ptr(), stage.data_ptr(), self.x0.data_ptr(), EB
         p.Hp, p.Wp, p.Hr, p.Wr, p.Cr, p.prec = r.Hp, r.Wp, h_, w_, c_, r.prec
         self.pts = p
+        # ---- smooth=: the per-row sigma, gt_sg_points in place of gt_ig_points, gt_sg_reduce in place of gt_ig_reduce
+        self.sigma = torch.zeros(EB, dtype=torch.float32, device=dev)
+        sp = K.SgPointsArgs()
+        sp.raw, sp.out, sp.sigma, sp.rows = self.raw.data_ptr(), stage.data_ptr(), self.sigma.data_ptr(), EB
+        sp.Hp, sp.Wp, sp.Hr, sp.Wr, sp.Cr, sp.prec = r.Hp, r.Wp, h_, w_, c_, r.prec
+        self.sg_pts = sp
+        sr = K.SgReduceArgs()
+        sr.dx, sr.x, sr.weight, sr.out = self.dx.data_ptr(), self.raw.data_ptr(), weight.data_ptr(), self.out.data_ptr()
+        sr.G, sr.B = G, EB
+        sr.Hp, sr.Wp, sr.Hr, sr.Wr, sr.Cr, sr.prec = r.Hp, r.Wp, h_, w_, c_, r.prec
+        self.sg_red = sr
 
     def forward(self, pred, rows, logit):
         """Masked forward and head of the staging tensor on the current stream: ``tgt`` / ``base`` / ``dH`` of the
@@ -1804,12 +1897,54 @@ class SaliencyState(object):
         else:
             self.tgt[:m].copy_(torch.from_numpy(target[s:s + m].astype(np.int32)).to(self.tgt.device))
 
-    def run(self, pred, x, target, score, method, steps, x0, reduce):
+    def run_smooth(self, pred, x, target, score, method, reduce, smooth):
+        """:meth:`run` with ``smooth`` (:func:`smooth_spec`'s tuple): per chunk of ``R = EB // S`` images one
+        upload, a forward of the clean images (label and base score), ``gt_sg_points``, one launch set over the
+        ``S * R`` points and ``gt_sg_reduce``; a short last chunk runs ``S * mm`` points only."""
+        S, noise, seed, stat = smooth
+        n, EB, dev, K = x.shape[0], pred.EB, pred.device, pred.K
+        h, w, c = pred.hwc
+        logit = 1 if score == "logit" else 0
+        per = h * w * (c if reduce is None else 1)
+        R = EB // S
+        sigma = torch.from_numpy(smooth_sigma(x, noise))
+        sp, sr = self.sg_pts, self.sg_red
+        sp.S, sp.seed = S, seed
+        sr.S, sr.inv_s = S, float(np.float32(1) / np.float32(S))
+        sr.stat, sr.method = SG_STATS.index(stat), SG_METHODS.index(method)
+        sr.reduce = {None: 0, "absmax": 1, "sum": 2}[reduce]
+        with torch.cuda.device(dev):
+            out = torch.empty(n * per, dtype=torch.float32, device=dev)
+            tgt = torch.empty(n, dtype=torch.int32, device=dev)
+            base = torch.empty(n, dtype=torch.float32, device=dev)
+            for s in range(0, n, R):
+                mm = min(R, n - s)
+                pred.upload(x[s:s + mm])
+                self._set_targets(target, s, mm)
+                self.forward(pred, mm, logit)                            # label and base score of the clean images
+                tgt[s:s + mm].copy_(self.tgt[:mm])
+                base[s:s + mm].copy_(self.base[:mm])
+                self.raw[:mm].copy_(pred.stage[:mm])
+                self.tgt[:S * mm].copy_(self.tgt[:mm].repeat(S))         # row k * mm + r: the target of image r
+                self.sigma[:mm].copy_(sigma[s:s + mm].to(dev))
+                sp.R, sp.n0, sr.R = mm, s, mm
+                K.check(pred.job.L.gt_sg_points(sp, pred.job._stream()), "sg_points")
+                self.forward(pred, S * mm, logit)
+                self.backward(pred, S * mm)
+                K.check(pred.job.L.gt_sg_reduce(sr, pred.job._stream()), "sg_reduce")
+                out[s * per:(s + mm) * per].copy_(self.out[:mm * per])
+            shape = (n, h, w, c) if reduce is None else (n, h, w)
+            return (out.cpu().numpy().reshape(shape), tgt.cpu().numpy().astype(np.int64), base.cpu().numpy(), None)
+
+    def run(self, pred, x, target, score, method, steps, x0, reduce, smooth=None):
         """``x`` [n, H, W, C] host fp32 -> ``(map, target int64 [n], base fp32 [n], baseline_score or None)`` as
         host arrays. ``"gradient"`` / ``"gradxinput"``: per chunk of ``EB`` images one upload and one launch set.
         ``"integrated"``: per chunk of ``R = EB // steps`` images one upload, a forward of the images themselves
         (label and base score), ``gt_ig_points`` and one launch set over the ``steps * R`` points; one more
-        forward per call scores the baseline. Results gather on the device and are read back once."""
+        forward per call scores the baseline. Results gather on the device and are read back once. ``smooth``:
+        :meth:`run_smooth`."""
+        if smooth is not None:
+            return self.run_smooth(pred, x, target, score, method, reduce, smooth)
         n, EB, dev = x.shape[0], pred.EB, pred.device
         h, w, c = pred.hwc
         logit = 1 if score == "logit" else 0
@@ -1977,12 +2112,12 @@ class HipPredictor(object):
             self._one = torch.ones(1, dtype=torch.float32, device=self.device)
         return mc_state(self, 1, self._one).run(self, x, samples, dropout, seed, return_samples)
 
-    def saliency(self, x, target, score, method, steps, x0, reduce):
+    def saliency(self, x, target, score, method, steps, x0, reduce, smooth=None):
         """``(map, target, base, baseline_score)`` of validated arguments (``CnnClassifier.saliency``): one member
         of weight 1.0 (``1.0f * v`` is ``v``)."""
         if self._one is None:
             self._one = torch.ones(1, dtype=torch.float32, device=self.device)
-        return saliency_state(self, 1, self._one).run(self, x, target, score, method, steps, x0, reduce)
+        return saliency_state(self, 1, self._one).run(self, x, target, score, method, steps, x0, reduce, smooth)
 
     def run(self, x, views=None):
         """``x`` [n, H, W, C] host fp32 -> (logits, proba) host fp32 ``[n, classes]``; with ``views`` (a tuple

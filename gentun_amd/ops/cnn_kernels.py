@@ -9,6 +9,7 @@ import ctypes as C
 import os
 
 from . import _lib
+from ..utils.rng import SG_KEY
 
 P = C.c_void_p
 I = C.c_int
@@ -271,6 +272,25 @@ class IgReduceArgs(C.Structure):
                 ("inv_m", C.c_float)]
 
 
+SG_STATS = ("mean", "sq", "var")        # SgReduceArgs.stat: SmoothGrad, SmoothGrad^2, VarGrad
+SG_METHODS = ("gradient", "gradxinput")  # SgReduceArgs.method
+
+
+class SgPointsArgs(C.Structure):
+    """csrc/hip/cnn_smooth.hip SgPointsArgs: the Gaussian points of a raw chunk into the staging tensor
+    (gt_sg_points)."""
+    _fields_ = [("raw", P), ("out", P), ("sigma", P), ("R", I), ("S", I), ("rows", I), ("n0", I),
+                ("seed", C.c_uint), ("Hp", I), ("Wp", I), ("Hr", I), ("Wr", I), ("Cr", I), ("prec", I)]
+
+
+class SgReduceArgs(C.Structure):
+    """csrc/hip/cnn_smooth.hip SgReduceArgs: the points' input gradients -> the noise-averaged attribution map
+    of every raw row (gt_sg_reduce)."""
+    _fields_ = [("dx", P), ("x", P), ("weight", P), ("out", P), ("G", I), ("B", I), ("R", I), ("S", I),
+                ("Hp", I), ("Wp", I), ("Hr", I), ("Wr", I), ("Cr", I), ("stat", I), ("method", I), ("reduce", I),
+                ("prec", I), ("inv_s", C.c_float)]
+
+
 MC_MAX_SAMPLES = 64     # samples of one Monte-Carlo dropout request at most (csrc/hip/cnn_head_mc.hip MC_MAXT)
 
 
@@ -487,7 +507,9 @@ def lib():
                                  ("gt_conv_in_dgrad", "conv_in_dgrad", ConvInDgradArgs),
                                  ("gt_bn_bwd_eval", "bn_bwd_eval", BnBwdEvalArgs),
                                  ("gt_ig_points", "ig_points", IgPointsArgs),
-                                 ("gt_ig_reduce", "ig_reduce", IgReduceArgs)):
+                                 ("gt_ig_reduce", "ig_reduce", IgReduceArgs),
+                                 ("gt_sg_points", "sg_points", SgPointsArgs),
+                                 ("gt_sg_reduce", "sg_reduce", SgReduceArgs)):
             fn = getattr(L, fname)
             fn.argtypes = [C.POINTER(st), P]
             fn.restype = I
@@ -495,6 +517,9 @@ def lib():
             size.restype = C.c_size_t
             assert size() == C.sizeof(st), st.__name__ + " ABI mismatch"
         assert L.gt_ig_max_steps() == IG_MAX_STEPS, "IG_MAX_STEPS mismatch"
+        assert L.gt_sg_max_samples() == IG_MAX_STEPS, "smooth samples limit mismatch"
+        L.gt_sg_key.restype = C.c_uint
+        assert L.gt_sg_key() == SG_KEY, "SG_KEY mismatch"
         L.gt_occlude_views.argtypes = [C.POINTER(OccludeArgs), P]
         L.gt_occlude_views.restype = I
         L.gt_sizeof_occlude_args.restype = C.c_size_t

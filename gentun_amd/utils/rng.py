@@ -175,3 +175,27 @@ def mc_masks(seed, member, samples, rows, units, dropout):
     n = np.asarray(rows, dtype=np.uint64).reshape(1, -1, 1)
     u = np.arange(int(units), dtype=np.uint64)[None, None, :]
     return hash4(key, t, n, u) >= np.uint64(mc_threshold(dropout))
+
+
+SG_KEY = 0x534D4752        # xor of the seed in the key of the SmoothGrad noise draws ("SMGR")
+
+
+def sg_noise(seed, n, samples, hr, wr, cr):
+    """Standard normal draws of ``saliency(smooth=...)`` (csrc/hip/cnn_smooth.hip), fp64
+    ``[len(n), samples, hr, wr, cr]``: for image index ``n`` (its index within the call; an integer or an array
+    of them), sample ``k``, pixel ``p = i * wr + j`` and channel ``c``, Box-Muller's cosine branch
+    ``z = sqrt(-2 ln u_0) * cos(2 pi u_1)`` of ``u_j = ((r_j >> 9) * 2 + 1) * 2^-24`` with
+    ``r_j = hash4(seed ^ SG_KEY, n, k, (p * 4 + c) * 2 + j)``. ``u_j`` lies in (0, 1), so ``|z| <= 5.77``.
+    ``samples`` is the number of samples (``k = 0 .. samples - 1``) or a sequence of sample indices ``k``."""
+    import numpy as np
+    key = (int(seed) ^ SG_KEY) & _M32
+    nn = np.atleast_1d(np.asarray(n)).astype(np.uint64).reshape(-1, 1, 1, 1)
+    k = np.arange(samples) if np.ndim(samples) == 0 else np.asarray(samples)
+    k = k.astype(np.uint64).reshape(1, -1, 1, 1)
+    p = np.arange(int(hr) * int(wr), dtype=np.uint64).reshape(1, 1, -1, 1)
+    c = np.arange(int(cr), dtype=np.uint64).reshape(1, 1, 1, -1)
+    d = (p * np.uint64(4) + c) * np.uint64(2)
+    u = [((hash4(key, nn, k, d + np.uint64(j)) >> np.uint64(9)) * np.uint64(2) + np.uint64(1)).astype(np.float64)
+         * 2.0 ** -24 for j in range(2)]
+    z = np.sqrt(-2.0 * np.log(u[0])) * np.cos(2.0 * np.pi * u[1])
+    return z.reshape(nn.shape[0], k.shape[1], int(hr), int(wr), int(cr))

@@ -6,7 +6,12 @@ fitted for one epoch on ``--fit-rows`` glyph images, over ``--rows`` held-out 32
       the evaluation-mode backward chain, ``gt_conv_in_dgrad`` and ``gt_ig_reduce``;
 (ii)  plain HIP ``predict`` of the same rows -- the floor: the same uploads and forward launches;
 (iii) ``saliency(backend="torch")`` on the same GPU: stock-torch forward with autograd on the input;
-(iv)  ``saliency(method="integrated", steps=--steps)`` on the HIP predictor over the first ``--ig-rows`` rows.
+(iv)  ``saliency(method="integrated", steps=--steps)`` on the HIP predictor over the first ``--ig-rows`` rows;
+(v)   ``saliency(smooth={"samples": --samples})`` on the HIP predictor over the same ``--ig-rows`` rows: the points
+      drawn by ``gt_sg_points``, the statistics formed by ``gt_sg_reduce``;
+(vi)  the same map by hand: one ``predict`` for the labels, ``--samples`` plain HIP ``saliency`` calls on noisy copies
+      made on the host (``smooth_point``) and the numpy finish (``smooth_finish``);
+(vii) ``saliency(smooth=..., backend="torch")`` on the same GPU.
 
 Host array to host array, every call ending in a device synchronise; one warm-up call of every path, then the
 paths alternate run by run in this one process and the median of ``--reps`` runs is reported. One JSON line per
@@ -14,9 +19,11 @@ model as it finishes, then the whole result as the last line.
 
 ``--trace`` is the child of a kernel trace run of its own (``tools/gpu.sh cnn-saliency`` starts it under
 ``rocprofv3 --kernel-trace --stats``): it fits the models, calls ``saliency`` on ``--rows`` rows three times per model
-and exits; the trace's statistics then hold the kernels' own durations.
+and exits; the trace's statistics then hold the kernels' own durations. With ``--trace-smooth`` the three calls are
+those of (v) instead.
 
 usage: python tools/bench_cnn_saliency.py [--rows 10000] [--ig-rows 1000] [--steps 16] [--fit-rows 2000] [--k 4]
+                                            [--samples 16]
 """
 import argparse
 import json
@@ -34,6 +41,7 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--rows", type=int, default=10000)
 ap.add_argument("--ig-rows", type=int, default=1000)
 ap.add_argument("--steps", type=int, default=16)
+ap.add_argument("--samples", type=int, default=16)
 ap.add_argument("--fit-rows", type=int, default=2000)
 ap.add_argument("--k", type=int, default=4)
 ap.add_argument("--reps", type=int, default=5)
@@ -42,10 +50,12 @@ ap.add_argument("--dtype", choices=("fp32", "bf16"), default="fp32")
 ap.add_argument("--models", default="classifier,ensemble")
 ap.add_argument("--device", default="cuda:0")
 ap.add_argument("--trace", action="store_true", help="fit, call saliency three times per model and exit")
+ap.add_argument("--trace-smooth", action="store_true", help="--trace with the smooth calls of (v)")
 args = ap.parse_args()
 
 from gentun_amd.models.cnn import GeneticCnnModel  # noqa: E402
 from gentun_amd.models.cnn_ensemble import fit_ensemble  # noqa: E402
+from gentun_amd.models.cnn_fitted import saliency_reduce, smooth_finish, smooth_point, smooth_sigma  # noqa: E402
 from gentun_amd.utils.data import make_glyph_classification  # noqa: E402
 
 if not torch.cuda.is_available():
@@ -90,7 +100,20 @@ fx, fy = fx[:n_fit], fy[:n_fit]
 kw = dict(space, dropout_probability=0.5, nfold=5, epochs=(1,), learning_rate=(1e-3,), batch_size=32,
           dtype=args.dtype, seed=5, backend="hip")
 gs = genomes(args.k)
+smooth = {"samples": args.samples, "noise": 0.15, "seed": 0, "stat": "mean"}
+
+
+def by_hand(model, on):
+    """(vi): the SmoothGrad map of ``xi`` from plain calls and host work."""
+    t = model.predict(xi, output="label", **on)
+    sigma = smooth_sigma(xi, smooth["noise"])
+    g = [model.saliency(smooth_point(xi, sigma, smooth["seed"], k), target=t, reduce=None, **on)
+         for k in range(args.samples)]
+    return saliency_reduce(smooth_finish(g, xi, "gradient", "mean"), "absmax")
+
+
 result = {"metric": "saliency(), images/s", "rows": args.rows, "ig_rows": len(xi), "steps": args.steps,
+          "samples": args.samples,
           "fit_rows": n_fit, "dtype": args.dtype, "reps": args.reps, "batch": args.batch,
           "device": torch.cuda.get_device_name(dev), "cases": {}}
 with torch.cuda.device(dev):
@@ -100,10 +123,13 @@ with torch.cuda.device(dev):
     if "ensemble" in args.models:
         models.append((fit_ensemble(fx, fy, gs, device=dev, **kw), "ensemble_k{}".format(args.k)))
 
-    if args.trace:
+    if args.trace or args.trace_smooth:
         for model, name in models:
             for _ in range(3):
-                model.saliency(x, device=dev, batch=args.batch)
+                if args.trace_smooth:
+                    model.saliency(xi, device=dev, batch=args.batch, smooth=smooth)
+                else:
+                    model.saliency(x, device=dev, batch=args.batch)
             torch.cuda.synchronize(dev)
         print(json.dumps({"trace": [name for _, name in models], "rows": args.rows}), flush=True)
         sys.exit(0)
@@ -113,7 +139,10 @@ with torch.cuda.device(dev):
         paths = {"i_hip_gradient": (lambda: model.saliency(x, **on), args.rows),
                  "ii_hip_predict": (lambda: model.predict(x, output="proba", **on), args.rows),
                  "iii_torch_gradient": (lambda: model.saliency(x, backend="torch", **on), args.rows),
-                 "iv_hip_integrated": (lambda: model.saliency(xi, method="integrated", steps=args.steps, **on), len(xi))}
+                 "iv_hip_integrated": (lambda: model.saliency(xi, method="integrated", steps=args.steps, **on), len(xi)),
+                 "v_hip_smooth": (lambda: model.saliency(xi, smooth=smooth, **on), len(xi)),
+                 "vi_hip_smooth_by_hand": (lambda: by_hand(model, on), len(xi)),
+                 "vii_torch_smooth": (lambda: model.saliency(xi, smooth=smooth, backend="torch", **on), len(xi))}
         first, outs, total = {}, {}, {p: [] for p in paths}
         for p, (fn, _) in paths.items():                 # warm-up: predictors and states are built here
             first[p], outs[p] = timed(fn)
@@ -127,6 +156,9 @@ with torch.cuda.device(dev):
             rec[p] = dict(summary(total[p], rows), first_call_ms=round(first[p], 1))
         rec["i_over_ii"] = round(rec["i_hip_gradient"]["median_ms"] / rec["ii_hip_predict"]["median_ms"], 3)
         rec["iii_over_i"] = round(rec["iii_torch_gradient"]["median_ms"] / rec["i_hip_gradient"]["median_ms"], 3)
+        rec["vi_over_v"] = round(rec["vi_hip_smooth_by_hand"]["median_ms"] / rec["v_hip_smooth"]["median_ms"], 3)
+        rec["vii_over_v"] = round(rec["vii_torch_smooth"]["median_ms"] / rec["v_hip_smooth"]["median_ms"], 3)
+        rec["max_abs_diff_v_vs_vi"] = float(np.abs(outs["v_hip_smooth"] - outs["vi_hip_smooth_by_hand"]).max())
         result["cases"][name] = rec
         print(json.dumps({name: rec}), flush=True)
 print(json.dumps(result), flush=True)

@@ -57,6 +57,7 @@ HIP_EXTRA_FLAGS = {
     "cnn_head_mc.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
     "cnn_saliency.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
     "cnn_rise.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+    "cnn_smooth.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
 }
 
 

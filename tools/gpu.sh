@@ -296,7 +296,13 @@ cnn-saliency)
     python3 tools/bench_cnn_saliency.py --trace --rows ${ROWS:-10000} --fit-rows ${FIT_ROWS:-2000} --k ${K:-4} \
     ${SAL_ARGS:-} > $out/prof.log 2>&1 &&
   find /tmp/prof_sal -name "*kernel_stats.csv" -exec cp {} $out/kernel_stats.csv \; &&
-  grep -E "Name|conv_in_dgrad|head_saliency|ig_reduce|dense_dgrad|conv_fast|head_predict" $out/kernel_stats.csv | cut -c1-300; rc=$?
+  grep -E "Name|conv_in_dgrad|head_saliency|ig_reduce|dense_dgrad|conv_fast|head_predict" $out/kernel_stats.csv | cut -c1-300 &&
+  rm -rf /tmp/prof_sal &&
+  timeout -k 10 300 rocprofv3 --kernel-trace --stats -d /tmp/prof_sal -o run --output-format csv -- \
+    python3 tools/bench_cnn_saliency.py --trace-smooth --rows ${IG_ROWS:-1000} --ig-rows ${IG_ROWS:-1000} \
+    --samples ${SAMPLES:-16} --fit-rows ${FIT_ROWS:-2000} --k ${K:-4} ${SAL_ARGS:-} > $out/prof_smooth.log 2>&1 &&
+  find /tmp/prof_sal -name "*kernel_stats.csv" -exec cp {} $out/kernel_stats_smooth.csv \; &&
+  grep -E "Name|sg_points|sg_reduce|conv_in_dgrad|head_saliency" $out/kernel_stats_smooth.csv | cut -c1-300; rc=$?
   [ $rc -eq 0 ] || { tail -5 $out/bench.err $out/prof.log 2>/dev/null; cut -c1-2000 $out/bench.json; }
   exit $rc ;;
 rehearse)
