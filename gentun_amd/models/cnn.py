@@ -235,6 +235,20 @@ class GeneticCnnModel(GentunModel):
         kwargs.setdefault("device", self.device)
         return self.fitted.saliency(x, **kwargs)
 
+    def embed(self, x, **kwargs):
+        """``self.fitted.embed`` on this model's device unless ``device`` says otherwise."""
+        if self.fitted is None:
+            raise RuntimeError("GeneticCnnModel.embed before fit()")
+        kwargs.setdefault("device", self.device)
+        return self.fitted.embed(x, **kwargs)
+
+    def neighbors(self, x, bank, **kwargs):
+        """``self.fitted.neighbors`` on this model's device unless ``device`` says otherwise."""
+        if self.fitted is None:
+            raise RuntimeError("GeneticCnnModel.neighbors before fit()")
+        kwargs.setdefault("device", self.device)
+        return self.fitted.neighbors(x, bank, **kwargs)
+
     def predict_mc(self, x, **kwargs):
         """``self.fitted.predict_mc`` on this model's device and with this model's ``dropout_probability``
         unless ``device`` / ``dropout`` say otherwise."""

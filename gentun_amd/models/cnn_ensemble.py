@@ -24,8 +24,9 @@ import math
 import numpy as np
 import torch
 
-from .cnn_fitted import (CnnClassifier, TtaState, cam_check, cam_check_hip, cam_upsample, gradcam_state, mc_check,
-                         mc_check_hip, mc_result, mc_state, mc_statistics, occlusion_by_views, occlusion_fill,
+from .cnn_fitted import (CnnClassifier, TtaState, cam_check, cam_check_hip, cam_upsample, embed_run, gradcam_state,
+                         mc_check, mc_check_hip, mc_result, mc_state, mc_statistics, neighbors_run,
+                         occlusion_by_views, occlusion_fill,
                          occlusion_grid, occlusion_state, occlusion_targets, predict_batch, rise_by_views,
                          rise_check, rise_check_hip, rise_state, saliency_check,
                          saliency_check_hip, saliency_info, saliency_reduce, saliency_state, smooth_spec,
@@ -358,6 +359,18 @@ class CnnEnsemble(object):
                       for i, m in enumerate(self.members)])
         return mc_result(mc_statistics(p, self.weights), p if return_samples else None)
 
+    def embed(self, x, device=None, batch=256, backend=None):
+        """The ensemble's feature vectors (``CnnClassifier.embed``): the members' hidden rows side by side in
+        member order, fp32 ``[n, k * dense_units]``. The ensemble weights are not used: they weigh
+        probabilities, and a distance in the concatenated space counts every member alike."""
+        return embed_run(self, self.members, x, device, batch, backend)
+
+    def neighbors(self, x, bank, k=5, metric="l2", device=None, batch=256, backend=None):
+        """The ``k`` nearest rows of ``bank`` in the feature space of :meth:`embed`
+        (``CnnClassifier.neighbors``); on a ``cuda`` device the kernels read the members' hidden rows where
+        ``gt_dense_fwd`` wrote them, member after member, with no concatenation in between."""
+        return neighbors_run(self, self.members, x, bank, k, metric, device, batch, backend)
+
     def distill(self, x, y_onehot, genes=None, alpha=0.5, temperature=1.0, device=None, **additional_parameters):
         """Fit one student on a blend of the hard labels and this ensemble's probabilities
         (:func:`gentun_amd.models.cnn_distill.distill`). ``genes=None``: the first member's genes."""
@@ -416,6 +429,7 @@ class HipEnsemblePredictor(object):
             for g, m in enumerate(ens.members):
                 m.load_into(job, g)
             self.ops, self.df, _, self._keep = job._build_eval_ops(EB)
+            self.hidden = job._eval_hidden       # [k][EB][Up], what gt_dense_fwd writes
             self.gather = torch.arange(EB, dtype=torch.int64, device=self.device).repeat(k, 1).contiguous()
             for kind, b, _ in self.ops:
                 if kind == "conv" and b.gather:
@@ -441,6 +455,7 @@ class HipEnsemblePredictor(object):
         self._cam_wbar = None        # W1 summed over the real pixels (cam_wbar), on the first Grad-CAM request
         self._mc = None              # McState, created on the first Monte-Carlo dropout request
         self._sal = None             # SaliencyState, created on the first saliency request
+        self._nn = None              # NeighborState, created on the first embed / neighbors request
 
     def _host(self, ens, EB):
         from . import cnn_engine as E

@@ -637,6 +637,121 @@ def rise_check_hip(classes):
         raise ValueError("HIP head kernel supports at most 16 classes")
 
 
+NN_METRICS = ("l2", "cosine")
+NN_MAX_K = 16                # NN_MAXK of csrc/hip/cnn_neighbors.hip
+
+
+def embed_check(batch, backend):
+    """The validated ``batch`` of an ``embed`` / ``neighbors`` request; ``ValueError`` on a bad ``batch`` or
+    ``backend``."""
+    if not _is_int(batch) or int(batch) < 1:
+        raise ValueError("batch must be a positive integer")
+    if backend not in (None, "hip", "torch"):
+        raise ValueError("unknown backend {!r}".format(backend))
+    return int(batch)
+
+
+def neighbors_check(k, metric, bank, input_shape, D, batch, backend):
+    """The validated ``(k, metric, bank, images, batch)`` of a ``neighbors`` request, before any forward runs.
+    ``bank`` comes back as contiguous fp32, ``images`` says whether it holds images ``[N, H, W, C]`` (to embed) or
+    embeddings ``[N, D]``. ``ValueError`` on: ``k`` not an int in ``1..16`` or above ``N``; a metric outside
+    ``NN_METRICS``; a bank that is neither form, whose ``D`` is not the model's or whose embeddings are not
+    finite; a bad ``batch`` or ``backend``."""
+    if not _is_int(k) or not 1 <= int(k) <= NN_MAX_K:
+        raise ValueError("neighbors: k must be an integer in [1, {}], got {!r}".format(NN_MAX_K, k))
+    if metric not in NN_METRICS:
+        raise ValueError("neighbors: metric {!r}: expected one of {}".format(metric, NN_METRICS))
+    batch = embed_check(batch, backend)
+    bank = np.asarray(bank)
+    images = bank.ndim == 4
+    if images:
+        if tuple(bank.shape[1:]) != tuple(input_shape):
+            raise ValueError("neighbors: a bank of images must be [N, {}, {}, {}], got shape {}".format(
+                *(tuple(input_shape) + (bank.shape,))))
+    elif bank.ndim != 2:
+        raise ValueError("neighbors: bank must be images [N, H, W, C] or embeddings [N, D], got shape {}".format(
+            bank.shape))
+    elif bank.shape[1] != D:
+        raise ValueError("neighbors: the bank has {} features, the model's embedding has {}".format(bank.shape[1], D))
+    if int(k) > bank.shape[0]:
+        raise ValueError("neighbors: k = {} exceeds the bank's {} rows".format(k, bank.shape[0]))
+    bank = np.ascontiguousarray(bank, dtype=np.float32)
+    if not images and not np.isfinite(bank).all():
+        raise ValueError("neighbors: the bank's embeddings must be finite")
+    return int(k), metric, bank, images, batch
+
+
+def neighbors_search(q, b, k, metric, rows=1 << 22):
+    """``(index int64 [n, k], distance fp32 [n, k])`` of fp32 embeddings ``q [n, D]`` against ``b [N, D]``, the
+    definition every backend is held to: ``q.b``, ``|q|^2`` and ``|b|^2`` are fp64 sums over the features in
+    feature order (every product of two fp32 values is exact in fp64), the distance
+
+    * ``"l2"``: ``max(|q|^2 + |b|^2 - 2 q.b, 0)``
+    * ``"cosine"``: ``1 - q.b / (sqrt(|q|^2) sqrt(|b|^2))``, 1 when either norm is 0
+
+    is formed in fp64 and rounded to fp32 once, and the neighbours are the first ``k`` of a stable sort of the
+    fp32 distances: ascending ``(distance, bank index)``. The one summation order makes a query that is a bank row
+    its own neighbour at l2 distance exactly 0. ``rows``: (query, bank) pairs held at a time."""
+    q64, b64 = np.asarray(q, np.float64), np.asarray(b, np.float64)
+    n, N, D = q64.shape[0], b64.shape[0], q64.shape[1]
+    bb = np.zeros(N)
+    for d in range(D):
+        bb += b64[:, d] * b64[:, d]
+    idx, dist = np.empty((n, k), np.int64), np.empty((n, k), np.float32)
+    step = max(1, rows // max(N, 1))
+    for s in range(0, n, step):
+        qs = q64[s:s + step]
+        dot, qq = np.zeros((qs.shape[0], N)), np.zeros(qs.shape[0])
+        for d in range(D):
+            dot += np.multiply.outer(qs[:, d], b64[:, d])
+            qq += qs[:, d] * qs[:, d]
+        if metric == "l2":
+            dd = np.maximum(qq[:, None] + bb[None, :] - 2.0 * dot, 0.0)
+        else:
+            den = np.sqrt(qq)[:, None] * np.sqrt(bb)[None, :]
+            dd = np.where(den > 0.0, 1.0 - dot / np.where(den > 0.0, den, 1.0), 1.0)
+        d32 = dd.astype(np.float32)
+        order = np.argsort(d32, axis=1, kind="stable")[:, :k]
+        idx[s:s + step] = order
+        dist[s:s + step] = np.take_along_axis(d32, order, axis=1)
+    return idx, dist
+
+
+def _nn_backend(device, backend):
+    dev = torch.device("cpu" if device is None else device)
+    return dev, backend or ("hip" if dev.type == "cuda" else "torch")
+
+
+def embed_torch(members, x, dev, batch, dtype=torch.float32):
+    """The members' stock-torch embeddings side by side in member order, ``[n, len(members) * dense_units]``."""
+    return np.concatenate([m._torch_embed(x, dev, batch, dtype) for m in members], axis=1)
+
+
+def embed_run(model, members, x, device, batch, backend):
+    """``embed`` of a classifier (``members = [model]``) or an ensemble."""
+    batch = embed_check(batch, backend)
+    x = members[0]._check_x(x)
+    dev, backend = _nn_backend(device, backend)
+    if backend == "hip":
+        pred = model.hip_predictor(dev, batch)
+        return neighbor_state(pred, len(members)).embed(pred, x)
+    return embed_torch(members, x, dev, batch)
+
+
+def neighbors_run(model, members, x, bank, k, metric, device, batch, backend):
+    """``neighbors`` of a classifier (``members = [model]``) or an ensemble."""
+    first = members[0]
+    k, metric, bank, images, batch = neighbors_check(k, metric, bank, first.input_shape,
+                                                     len(members) * first.dense_units, batch, backend)
+    x = first._check_x(x)
+    dev, backend = _nn_backend(device, backend)
+    if backend == "hip":
+        pred = model.hip_predictor(dev, batch)
+        return neighbor_state(pred, len(members)).run(pred, x, bank, images, k, metric)
+    q = embed_torch(members, x, dev, batch)
+    return neighbors_search(q, embed_torch(members, bank, dev, batch) if images else bank, k, metric)
+
+
 def predict_batch(batch):
     """Rows per launch of the HIP predictor: ``batch`` rounded up to a multiple of 32, at least 32 and
     at most 256 (the cap of ``HipPopJob.eval_batch``)."""
@@ -1029,6 +1144,55 @@ class CnnClassifier(object):
             raise ValueError("unknown backend {!r}".format(backend))
         p = self._torch_mc(x, 0, samples, dropout, seed, dev, batch, torch.float32)[None]
         return mc_result(mc_statistics(p, np.ones(1, np.float32)), p if return_samples else None)
+
+    def embed(self, x, device=None, batch=256, backend=None):
+        """The feature vectors of ``x`` ``[n, H, W, C]`` (or one image), fp32 ``[n, dense_units]``: the post-ReLU
+        output of the dense hidden layer in evaluation mode (no dropout), real units only.
+
+        ``device`` / ``backend`` / ``batch`` as in :meth:`predict`: the CPU or ``backend="torch"`` runs the
+        stock-torch forward up to the hidden row; a ``cuda`` device runs the HIP predictor's forward and
+        ``gt_dense_fwd`` and copies the real units of its output."""
+        return embed_run(self, [self], x, device, batch, backend)
+
+    def neighbors(self, x, bank, k=5, metric="l2", device=None, batch=256, backend=None):
+        """The ``k`` (1..16) nearest rows of ``bank`` to every image of ``x`` in the feature space of
+        :meth:`embed`: ``(index int64 [n, k], distance fp32 [n, k])`` in ascending ``(distance, bank index)``
+        order, so a tie goes to the lower index. ``bank`` is images ``[N, H, W, C]``, embedded first, or fp32
+        embeddings ``[N, dense_units]`` from :meth:`embed` (embed a bank once, search it many times).
+        ``metric="l2"`` is the squared Euclidean distance ``max(|q|^2 + |b|^2 - 2 q.b, 0)``, ``"cosine"`` is
+        ``1 - q.b / (|q| |b|)``, 1 when either norm is 0. Arguments are checked before any forward runs
+        (:func:`neighbors_check`).
+
+        The CPU or ``backend="torch"`` embeds by stock torch and searches on the host in fp64
+        (:func:`neighbors_search`, the definition). A ``cuda`` device keeps the bank on the device as bf16
+        planes (``gt_nn_bank``) and runs the product on the matrix cores with the selection fused
+        (``gt_nn_topk``, ``gt_nn_merge``; csrc/hip/cnn_neighbors.hip) at fp32 accuracy: a distance is within
+        the split-fp32 bound of the definition's and depends on its own query and bank row only, so results do
+        not change with ``batch``; where two distances differ by less than the bound the order may differ from
+        the host's. A bf16 fit rounds a bank of fp32 embeddings to bf16. A bank whose planes would pass 1 GiB on
+        the device is a ``ValueError`` that names ``backend="torch"``.
+
+        The host search is the definition, not a fast path: it updates all ``n x N`` sums once per feature, which
+        is seconds for 1,000 x 10,000 x 500 and many minutes at 10,000 x 50,000 x 500 -- split such a bank and
+        merge the results, or search it on the device. A bank row whose distance overflows to ``+inf`` is never
+        returned by the device; a query with fewer than ``k`` finite distances gets ``(2^31 - 1, +inf)`` there."""
+        return neighbors_run(self, [self], x, bank, k, metric, device, batch, backend)
+
+    def _torch_embed(self, x, dev, batch, dtype):
+        """``embed`` by stock torch in ``dtype`` (fp32, or fp64: the tests' oracle): the chunks of
+        :meth:`_torch_predict` up to the hidden row."""
+        P = self._tensors(dev, dtype)
+        n = x.shape[0]
+        h, w, c = self.input_shape
+        out = np.empty((n, self.dense_units), np.float64 if dtype == torch.float64 else np.float32)
+        with torch.no_grad():
+            for s in range(0, n, batch):
+                m = min(batch, n - s)
+                buf = np.zeros(((m + 31) // 32 * 32, c, h, w), np.float32)
+                buf[:m] = x[s:s + m].transpose(0, 3, 1, 2)
+                hid = self._torch_hidden(self._torch_features(torch.from_numpy(buf).to(device=dev, dtype=dtype), P), P)
+                out[s:s + m] = hid[:m].cpu().numpy()
+        return out
 
     def hip_predictor(self, device, batch=256):
         """The cached :class:`HipPredictor` of (device, rows per launch)."""
@@ -1714,6 +1878,134 @@ def mc_state(pred, G, weight):
     return pred._mc
 
 
+def nn_slices(tiles, qtiles, cus):
+    """Bank slices of one ``gt_nn_topk`` launch: enough workgroups (query tiles x slices) for two per compute
+    unit, at most one slice per bank tile and ``NN_MAX_SLICES``. Any value gives the same bits."""
+    from ..ops.cnn_kernels import NN_MAX_SLICES
+    return int(max(1, min(NN_MAX_SLICES, tiles, -(-2 * cus // qtiles))))
+
+
+def nn_bank_rows(N, Dp, npl):
+    """Rows of the resident bank of ``N`` rows, ``N`` rounded up to the bank tile; ``ValueError`` (before any
+    forward or allocation) when its ``npl`` bf16 planes of ``Dp`` stored features pass the launchers' 1 GiB."""
+    from ..ops.cnn_kernels import NN_BANK_TILE, NN_MAX_PLANE_BYTES
+    Np = -(-N // NN_BANK_TILE) * NN_BANK_TILE
+    if npl * Np * Dp * 2 > NN_MAX_PLANE_BYTES:
+        raise ValueError("neighbors: a bank of {} rows x {} stored features takes {:.2f} GiB of planes on the "
+                         "device, above the HIP path's 1 GiB; use backend=\"torch\"".format(
+                             N, Dp, npl * Np * Dp * 2.0 / 2 ** 30))
+    return Np
+
+
+class NeighborState(object):
+    """What a HIP predictor (``HipPredictor`` or ``HipEnsemblePredictor``) adds for ``embed`` / ``neighbors``: a
+    view of the hidden activations ``gt_dense_fwd`` writes in evaluation mode (``[G][EB][Up]``) and the argument
+    structs of csrc/hip/cnn_neighbors.hip over it. The predictor's job, evaluation launches, staging tensor and
+    ``upload`` are used as they are, at ``EB`` rows. The bank of a request lives for that request only."""
+
+    FLAT_ROWS = 8192             # rows of a host bank uploaded at a time
+
+    def __init__(self, pred, G):
+        job = pred.job
+        self.G, self.Up, self.Ur, self.prec = G, job.Up, job.members[0][0].dense_units, int(pred.df.prec)
+        self.hidden = pred.hidden
+        assert self.hidden.data_ptr() == pred.df.out and tuple(self.hidden.shape) == (G, pred.EB, self.Up)
+        self.cus = torch.cuda.get_device_properties(pred.device).multi_processor_count
+
+    def _src(self, pred):
+        s = pred.K.NnSrc()
+        s.h, s.G, s.B, s.Up, s.Ur, s.flat, s.ld = pred.df.out, self.G, pred.EB, self.Up, self.Ur, 0, 0
+        return s
+
+    def forward(self, pred, chunk):
+        """One chunk into the staging tensor and through the evaluation launches up to the hidden rows; the
+        launches' stream comes back."""
+        job = pred.job
+        pred.upload(chunk)
+        st = job._stream()
+        job._run_fwd(st, pred.ops)
+        pred.K.check(job.L.gt_dense_fwd(pred.df, st), "dense_fwd(embed)")
+        return st
+
+    def embed(self, pred, x):
+        """``x`` [n, H, W, C] host fp32 -> [n, G * Ur] host fp32: the real units of every member, member order."""
+        n, EB = x.shape[0], pred.EB
+        with torch.cuda.device(pred.device):
+            out = torch.empty((n, self.G, self.Ur), dtype=torch.float32, device=pred.device)
+            for s in range(0, n, EB):
+                m = min(EB, n - s)
+                self.forward(pred, x[s:s + m])
+                out[s:s + m].copy_(self.hidden[:, :m, :self.Ur].permute(1, 0, 2))
+            return out.view(n, self.G * self.Ur).cpu().numpy()
+
+    def bank(self, pred, bank, images):
+        """The resident bank of a request, ``(planes, norm, N, Np)``: per chunk of ``EB`` images the forward and
+        ``gt_nn_bank`` over the hidden rows, or per ``FLAT_ROWS`` rows of host embeddings one upload and the same
+        kernel over the fp32 buffer; the last launch also writes the zero rows up to ``Np``."""
+        K, L, dev = pred.K, pred.job.L, pred.device
+        N, Dp, npl = bank.shape[0], self.G * self.Up, 3 if self.prec else 1
+        Np = nn_bank_rows(N, Dp, npl)
+        planes = torch.empty((npl, Np, Dp), dtype=torch.bfloat16, device=dev)
+        norm = torch.empty(Np, dtype=torch.float32, device=dev)
+        a = K.NnBankArgs()
+        a.planes, a.norm, a.prec, a.N, a.Np = planes.data_ptr(), norm.data_ptr(), self.prec, N, Np
+        if images:
+            a.src, a.sprec, step = self._src(pred), self.prec, pred.EB
+        else:
+            ld = -(-bank.shape[1] // 32) * 32
+            step = min(self.FLAT_ROWS, N)
+            buf = torch.zeros((step, ld), dtype=torch.float32, device=dev)
+            s = a.src
+            s.h, s.G, s.B, s.Up, s.Ur, s.flat, s.ld = buf.data_ptr(), self.G, step, self.Up, self.Ur, 1, ld
+            a.sprec = 1
+        for s0 in range(0, N, step):
+            m = min(step, N - s0)
+            if images:
+                st = self.forward(pred, bank[s0:s0 + m])
+            else:
+                buf[:m, :bank.shape[1]].copy_(torch.from_numpy(bank[s0:s0 + m]).to(dev))
+                st = pred.job._stream()
+            a.m, a.n0, a.rows = m, s0, (Np - s0 if s0 + m == N else m)
+            K.check(L.gt_nn_bank(a, st), "nn_bank")
+        return planes, norm, N, Np
+
+    def run(self, pred, x, bank, images, k, metric, slices=None):
+        """``(index int64 [n, k], distance fp32 [n, k])`` of validated arguments: the bank, then per chunk of
+        ``EB`` queries the forward, ``gt_nn_topk`` over ``slices`` bank slices (:func:`nn_slices` unless given)
+        and ``gt_nn_merge`` into the request's results, which are read back once."""
+        K, L, dev, EB = pred.K, pred.job.L, pred.device, pred.EB
+        n = x.shape[0]
+        with torch.cuda.device(dev):
+            planes, norm, N, Np = self.bank(pred, bank, images)
+            S = nn_slices(Np // K.NN_BANK_TILE, EB // 32, self.cus) if slices is None else int(slices)
+            cand_d = torch.empty((EB, S, k), dtype=torch.float32, device=dev)
+            cand_i = torch.empty((EB, S, k), dtype=torch.int32, device=dev)
+            idx = torch.empty((n, k), dtype=torch.int32, device=dev)
+            dist = torch.empty((n, k), dtype=torch.float32, device=dev)
+            t = K.NnTopkArgs()
+            t.q, t.planes, t.bnorm = self._src(pred), planes.data_ptr(), norm.data_ptr()
+            t.cand_d, t.cand_i = cand_d.data_ptr(), cand_i.data_ptr()
+            t.prec, t.N, t.Np, t.k, t.S, t.metric = self.prec, N, Np, k, S, NN_METRICS.index(metric)
+            g = K.NnMergeArgs()
+            g.cand_d, g.cand_i, g.S, g.k = t.cand_d, t.cand_i, S, k
+            for s in range(0, n, EB):
+                m = min(EB, n - s)
+                st = self.forward(pred, x[s:s + m])
+                t.m = g.m = m
+                g.out_d, g.out_i = dist[s:].data_ptr(), idx[s:].data_ptr()
+                K.check(L.gt_nn_topk(t, st), "nn_topk")
+                K.check(L.gt_nn_merge(g, st), "nn_merge")
+            return idx.cpu().numpy().astype(np.int64), dist.cpu().numpy()
+
+
+def neighbor_state(pred, G):
+    """The cached :class:`NeighborState` of a predictor (its ``_nn``), built on the first request."""
+    if pred._nn is None:
+        with torch.cuda.device(pred.device):
+            pred._nn = NeighborState(pred, G)
+    return pred._nn
+
+
 def saliency_info(res, method):
     """The ``return_info`` dict of ``(map, target, base, baseline_score)``."""
     info = {"target": res[1], "base": res[2]}
@@ -2040,6 +2332,7 @@ class HipPredictor(object):
         with torch.cuda.device(self.device):
             clf.load_into(job, 0)
             self.ops, self.df, _, self._keep = job._build_eval_ops(self.EB)
+            self.hidden = job._eval_hidden       # [1][EB][Up], what gt_dense_fwd writes
             self.gather = torch.arange(self.EB, dtype=torch.int64, device=self.device)
             for kind, b, _ in self.ops:
                 if kind == "conv" and b.gather:
@@ -2059,6 +2352,7 @@ class HipPredictor(object):
         self._cam_wbar = None        # W1 summed over the real pixels (cam_wbar), on the first Grad-CAM request
         self._mc = None              # McState, created on the first Monte-Carlo dropout request
         self._sal = None             # SaliencyState, created on the first saliency request
+        self._nn = None              # NeighborState, created on the first embed / neighbors request
 
     def forward(self):
         """The launches of one chunk on the current stream: staging tensor -> ``logits`` / ``proba``."""

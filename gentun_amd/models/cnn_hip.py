@@ -1177,6 +1177,7 @@ class HipPopJob(FoldJob):
         hd.h, hd.plog = hdrop.data_ptr(), plog.data_ptr()
         hd.B, hd.eval, hd.st = EB, 1, self.eval_state.data_ptr()
         self._eval_remap = (EB, dict(remap))     # training buffer -> its twin, for whoever adds launches over the twins
+        self._eval_hidden = hdrop                # [Q][EB][Up]: what df.out points at (the predictors' embeddings)
         return ops, df, hd, keep
 
     def evaluate(self):

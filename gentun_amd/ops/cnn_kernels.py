@@ -335,6 +335,34 @@ class HeadRiseArgs(C.Structure):
                 ("C", I), ("m", I), ("masks", I), ("Kp", I), ("w0", I), ("logit", I)]
 
 
+NN_MAX_K = 16           # neighbours of one request at most (csrc/hip/cnn_neighbors.hip NN_MAXK)
+NN_MAX_SLICES = 64      # bank slices of one gt_nn_topk launch at most (NN_MAXS)
+NN_BANK_TILE = 128      # bank rows are padded to this (NN_BT)
+NN_MAX_PLANE_BYTES = 1 << 30
+
+
+class NnSrc(C.Structure):
+    """csrc/hip/cnn_neighbors.hip NnSrc: gt_dense_fwd's output [G][B][Up], or (flat) fp32 [rows][ld]."""
+    _fields_ = [("h", P), ("G", I), ("B", I), ("Up", I), ("Ur", I), ("flat", I), ("ld", I)]
+
+
+class NnBankArgs(C.Structure):
+    """csrc/hip/cnn_neighbors.hip NnBankArgs: rows of features -> bank planes and squared norms (gt_nn_bank)."""
+    _fields_ = [("src", NnSrc), ("planes", P), ("norm", P), ("prec", I), ("sprec", I), ("m", I), ("rows", I),
+                ("n0", I), ("N", I), ("Np", I)]
+
+
+class NnTopkArgs(C.Structure):
+    """csrc/hip/cnn_neighbors.hip NnTopkArgs: queries x bank -> the k nearest per bank slice (gt_nn_topk)."""
+    _fields_ = [("q", NnSrc), ("planes", P), ("bnorm", P), ("cand_d", P), ("cand_i", P), ("prec", I), ("m", I),
+                ("N", I), ("Np", I), ("k", I), ("S", I), ("metric", I)]
+
+
+class NnMergeArgs(C.Structure):
+    """csrc/hip/cnn_neighbors.hip NnMergeArgs: the slices' lists of every query merged (gt_nn_merge)."""
+    _fields_ = [("cand_d", P), ("cand_i", P), ("out_d", P), ("out_i", P), ("m", I), ("S", I), ("k", I)]
+
+
 class DenseDgradArgs(C.Structure):
     _fields_ = [("dH", P), ("wt", P), ("dx", P), ("G", I), ("B", I), ("Fp", I), ("Up", I), ("prec", I),
                 ("wps", C.c_long), ("unpool_mask", P), ("unpool_x0", P), ("unpool_x1", P), ("unpool_sel", P),
@@ -535,6 +563,17 @@ def lib():
             size = getattr(L, "gt_sizeof_{}_args".format(sname))
             size.restype = C.c_size_t
             assert size() == C.sizeof(st), st.__name__ + " ABI mismatch"
+        for fname, sname, st in (("gt_nn_bank", "nn_bank", NnBankArgs), ("gt_nn_topk", "nn_topk", NnTopkArgs),
+                                 ("gt_nn_merge", "nn_merge", NnMergeArgs)):
+            fn = getattr(L, fname)
+            fn.argtypes = [C.POINTER(st), P]
+            fn.restype = I
+            size = getattr(L, "gt_sizeof_{}_args".format(sname))
+            size.restype = C.c_size_t
+            assert size() == C.sizeof(st), st.__name__ + " ABI mismatch"
+        assert L.gt_nn_max_k() == NN_MAX_K, "NN_MAX_K mismatch"
+        assert L.gt_nn_max_slices() == NN_MAX_SLICES, "NN_MAX_SLICES mismatch"
+        assert L.gt_nn_bank_tile() == NN_BANK_TILE, "NN_BANK_TILE mismatch"
         assert L.gt_rise_max_masks() == RISE_MAX_MASKS, "RISE_MAX_MASKS mismatch"
         assert L.gt_rise_max_cells() == RISE_MAX_CELLS, "RISE_MAX_CELLS mismatch"
         L.gt_adam_segments.argtypes = [C.POINTER(AdamArgs), I, P]

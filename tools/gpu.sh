@@ -26,6 +26,7 @@
 #   bash tools/gpu.sh cnn-gradcam             gradcam(): forward + gt_head_gradcam vs plain HIP predict (the floor) vs stock-torch autograd vs occlusion(patch=4), classifier and k-ensemble; the new kernels' device time by events and by a kernel trace run of its own (ROWS= OCC_ROWS= FIT_ROWS= K= REPS= OUT= TIME=)
 #   bash tools/gpu.sh cnn-saliency            saliency(): masked forward + backward chain + gt_conv_in_dgrad vs plain HIP predict (the floor) vs the stock-torch backend, integrated gradients on IG_ROWS rows, classifier and k-ensemble; the kernels' device time by a kernel trace run of its own (ROWS= IG_ROWS= STEPS= FIT_ROWS= K= REPS= OUT= TIME=)
 #   bash tools/gpu.sh cnn-mc                predict_mc(): forward + gt_head_mc vs plain HIP predict (the floor) vs the stock-torch backend, classifier and k-ensemble; the kernel's device time by a kernel trace run of its own (ROWS= SAMPLES= FIT_ROWS= K= REPS= OUT= TIME=)
+#   bash tools/gpu.sh cnn-neighbors         neighbors(): forwards + gt_nn_bank / gt_nn_topk / gt_nn_merge vs HIP embed + torch.cdist + topk vs HIP embed + a host search, classifier and k-ensemble; the kernels' device time by a kernel trace run of its own (ROWS= BANK= K= FIT_ROWS= MEMBERS= REPS= OUT= TIME=)
 #   bash tools/gpu.sh rehearse                2-rank torchrun bench on one GPU (gloo control plane)
 #   bash tools/gpu.sh secondary               bench lines: reference fold semantics, torch comparator
 #
@@ -282,6 +283,21 @@ cnn-mc)
     --k ${K:-4} ${MC_ARGS:-} > $out/prof.log 2>&1 &&
   find /tmp/prof_mc -name "*kernel_stats.csv" -exec cp {} $out/kernel_stats.csv \; &&
   grep -E "Name|head_mc|head_predict|head_ensemble|dense_fwd" $out/kernel_stats.csv | cut -c1-300; rc=$?
+  [ $rc -eq 0 ] || { tail -5 $out/bench.err $out/prof.log 2>/dev/null; cut -c1-2000 $out/bench.json; }
+  exit $rc ;;
+cnn-neighbors)
+  # the result line, then the kernels' own durations from a kernel trace of one child run of its own (fits, then
+  # two neighbors calls per model); the files are kept under $OUT
+  out=${OUT:-/tmp/cnn_neighbors}; heartbeat; mkdir -p $out; rocprof_env; rm -rf /tmp/prof_nn
+  timeout -k 10 ${TIME:-600} python -u tools/bench_cnn_neighbors.py --rows ${ROWS:-10000} --bank ${BANK:-50000} \
+    --k ${K:-5} --fit-rows ${FIT_ROWS:-2000} --members ${MEMBERS:-4} --reps ${REPS:-5} ${NN_ARGS:-} \
+    > $out/bench.json 2> $out/bench.err &&
+  tail -1 $out/bench.json | cut -c1-8000 &&
+  timeout -k 10 300 rocprofv3 --kernel-trace --stats -d /tmp/prof_nn -o run --output-format csv -- \
+    python3 tools/bench_cnn_neighbors.py --trace --rows ${ROWS:-10000} --bank ${BANK:-50000} --k ${K:-5} \
+    --fit-rows ${FIT_ROWS:-2000} --members ${MEMBERS:-4} ${NN_ARGS:-} > $out/prof.log 2>&1 &&
+  find /tmp/prof_nn -name "*kernel_stats.csv" -exec cp {} $out/kernel_stats.csv \; &&
+  grep -E "Name|nn_topk|nn_bank|nn_merge|dense_fwd" $out/kernel_stats.csv | cut -c1-300; rc=$?
   [ $rc -eq 0 ] || { tail -5 $out/bench.err $out/prof.log 2>/dev/null; cut -c1-2000 $out/bench.json; }
   exit $rc ;;
 cnn-saliency)
