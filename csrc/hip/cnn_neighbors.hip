@@ -26,6 +26,7 @@
 // (or is NaN) enters no list: a query with fewer than k finite distances gets (+inf, NN_NOIDX) in the places left.
 
 #include "common.h"
+#include "cnn_nn_src.h"
 
 #define NN_MAXK 16
 #define NN_MAXS 64
@@ -35,13 +36,6 @@
 #define NN_LISTS 512         // selection lists per workgroup: 16 per query, two per lane
 #define NN_NOIDX 0x7fffffff  // index of an empty list entry (distance +inf): sorts after every real pair
 #define NN_MAX_PLANE_BYTES (1L << 30)
-
-// where the features of a row live: gt_dense_fwd's output [G][B][Up], or (flat) a host array uploaded as
-// [rows][ld] fp32 with member g's real units at columns g * Ur ..
-struct NnSrc {
-  const void* h;
-  int G, B, Up, Ur, flat, ld;
-};
 
 struct NnBankArgs {
   NnSrc src;                 // src.B rows are readable; row r of the launch is bank row n0 + r
@@ -69,24 +63,6 @@ struct NnMergeArgs {
   int* out_i;                // [m][k]
   int m, S, k;
 };
-
-// the 8 features of chunk c (of Dp / 8) of one row as fp32; padding units are zeros whatever the memory holds
-template <int SP>
-__device__ __forceinline__ void nn_chunk(const NnSrc& s, int row, int c, float* f) {
-  const int cpu = s.Up >> 3;
-  const int g = c / cpu, u = (c - g * cpu) * 8;
-  if (s.flat) {
-    const float* p = static_cast<const float*>(s.h) + (int64_t)row * s.ld + g * s.Ur + u;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) f[e] = u + e < s.Ur ? p[e] : 0.f;
-    return;
-  }
-  const int64_t at = ((int64_t)g * s.B + row) * s.Up + u;
-  if (SP) load8f(static_cast<const float*>(s.h) + at, f);
-  else unpack8(*reinterpret_cast<const uint4*>(static_cast<const uint16_t*>(s.h) + at), f);
-#pragma unroll
-  for (int e = 0; e < 8; ++e) f[e] = u + e < s.Ur ? f[e] : 0.f;
-}
 
 __device__ __forceinline__ float nn_sq8(float s, const float* f) {
 #pragma clang fp contract(off)
@@ -367,14 +343,6 @@ __global__ void __launch_bounds__(256) nn_merge_kernel(const NnMergeArgs a) {
   const int64_t at = ((int64_t)query * a.S + (have ? s : 0)) * a.k;
   nn_merge_lists<64>(a.cand_d + at, a.cand_i + at, 1, have, a.k, a.out_d + (int64_t)query * a.k,
                      a.out_i + (int64_t)query * a.k, s == 0);
-}
-
-static bool nn_src_ok(const NnSrc& s, int rows, int sprec) {
-  if (!s.h || s.G < 1 || s.Up < 32 || s.Up % 32 || s.Ur < 1 || s.Ur > s.Up) return false;
-  if ((long)s.G * s.Up > (1L << 20) || rows < 1 || rows > s.B) return false;
-  if (s.flat != 0 && s.flat != 1) return false;
-  if (s.flat && (sprec != 1 || s.ld < s.G * s.Ur)) return false;
-  return true;
 }
 
 static bool nn_bank_ok(int prec, int N, int Np, long Dp) {

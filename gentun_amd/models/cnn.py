@@ -249,6 +249,20 @@ class GeneticCnnModel(GentunModel):
         kwargs.setdefault("device", self.device)
         return self.fitted.neighbors(x, bank, **kwargs)
 
+    def gaussian_fit(self, bank, **kwargs):
+        """``self.fitted.gaussian_fit`` on this model's device unless ``device`` says otherwise."""
+        if self.fitted is None:
+            raise RuntimeError("GeneticCnnModel.gaussian_fit before fit()")
+        kwargs.setdefault("device", self.device)
+        return self.fitted.gaussian_fit(bank, **kwargs)
+
+    def mahalanobis(self, x, stats, **kwargs):
+        """``self.fitted.mahalanobis`` on this model's device unless ``device`` says otherwise."""
+        if self.fitted is None:
+            raise RuntimeError("GeneticCnnModel.mahalanobis before fit()")
+        kwargs.setdefault("device", self.device)
+        return self.fitted.mahalanobis(x, stats, **kwargs)
+
     def predict_mc(self, x, **kwargs):
         """``self.fitted.predict_mc`` on this model's device and with this model's ``dropout_probability``
         unless ``device`` / ``dropout`` say otherwise."""

@@ -24,7 +24,8 @@ import math
 import numpy as np
 import torch
 
-from .cnn_fitted import (CnnClassifier, TtaState, cam_check, cam_check_hip, cam_upsample, embed_run, gradcam_state,
+from .cnn_fitted import (CnnClassifier, TtaState, cam_check, cam_check_hip, cam_upsample, embed_run,
+                         gaussian_fit_run, gradcam_state, mahalanobis_run,
                          mc_check, mc_check_hip, mc_result, mc_state, mc_statistics, neighbors_run,
                          occlusion_by_views, occlusion_fill,
                          occlusion_grid, occlusion_state, occlusion_targets, predict_batch, rise_by_views,
@@ -371,6 +372,17 @@ class CnnEnsemble(object):
         ``gt_dense_fwd`` wrote them, member after member, with no concatenation in between."""
         return neighbors_run(self, self.members, x, bank, k, metric, device, batch, backend)
 
+    def gaussian_fit(self, bank, labels=None, shrink=0.01, device=None, batch=256, backend=None):
+        """One Gaussian set per member (``CnnClassifier.gaussian_fit``): the ensemble's covariance is
+        block-diagonal by definition, no ``kU x kU`` matrix is formed; the arrays of ``stats`` lead with the
+        ``k`` members. ``bank`` is images or embeddings ``[N, k * dense_units]`` from :meth:`embed`."""
+        return gaussian_fit_run(self, self.members, bank, labels, shrink, device, batch, backend)
+
+    def mahalanobis(self, x, stats, device=None, batch=256, backend=None):
+        """The weighted mean of the members' squared Mahalanobis distances (``CnnClassifier.mahalanobis``),
+        taken in member order in fp32 like the ensemble's other means."""
+        return mahalanobis_run(self, self.members, self.weights, x, stats, device, batch, backend)
+
     def distill(self, x, y_onehot, genes=None, alpha=0.5, temperature=1.0, device=None, **additional_parameters):
         """Fit one student on a blend of the hard labels and this ensemble's probabilities
         (:func:`gentun_amd.models.cnn_distill.distill`). ``genes=None``: the first member's genes."""
@@ -456,6 +468,7 @@ class HipEnsemblePredictor(object):
         self._mc = None              # McState, created on the first Monte-Carlo dropout request
         self._sal = None             # SaliencyState, created on the first saliency request
         self._nn = None              # NeighborState, created on the first embed / neighbors request
+        self._gauss = None           # GaussianState, created on the first gaussian_fit / mahalanobis request
 
     def _host(self, ens, EB):
         from . import cnn_engine as E

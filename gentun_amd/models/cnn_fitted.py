@@ -752,6 +752,174 @@ def neighbors_run(model, members, x, bank, k, metric, device, batch, backend):
     return neighbors_search(q, embed_torch(members, bank, dev, batch) if images else bank, k, metric)
 
 
+GAUSS_KEYS = ("count", "mean", "cov", "whiten", "wmean", "shrink")
+
+
+def gaussian_check(labels, shrink, bank, input_shape, classes, D, batch, backend):
+    """The validated ``(labels int64 [N], C, shrink, bank, images, batch)`` of a ``gaussian_fit`` request, before
+    any forward runs. ``labels=None`` is one Gaussian for the whole bank (``C = 1``, all-zero labels); otherwise
+    ``C = classes`` and ``labels`` is an int array ``[N]`` in ``0..classes-1`` or one-hot ``[N, classes]``.
+    ``ValueError`` on labels of another form, length or range; ``shrink`` outside ``[0, 1]``; a bank that is
+    neither images of the model's shape nor finite embeddings ``[N, D]``, or that is empty; a bad ``batch`` or
+    ``backend``."""
+    batch = embed_check(batch, backend)
+    if isinstance(shrink, bool) or not isinstance(shrink, (int, float, np.integer, np.floating)) \
+            or not 0.0 <= float(shrink) <= 1.0:
+        raise ValueError("gaussian_fit: shrink must be a number in [0, 1], got {!r}".format(shrink))
+    bank = np.asarray(bank)
+    images = bank.ndim == 4
+    if images:
+        if tuple(bank.shape[1:]) != tuple(input_shape):
+            raise ValueError("gaussian_fit: a bank of images must be [N, {}, {}, {}], got shape {}".format(
+                *(tuple(input_shape) + (bank.shape,))))
+    elif bank.ndim != 2:
+        raise ValueError("gaussian_fit: bank must be images [N, H, W, C] or embeddings [N, D], got shape {}".format(
+            bank.shape))
+    elif bank.shape[1] != D:
+        raise ValueError("gaussian_fit: the bank has {} features, the model's embedding has {}".format(
+            bank.shape[1], D))
+    N = bank.shape[0]
+    if N < 1:
+        raise ValueError("gaussian_fit: the bank is empty")
+    bank = np.ascontiguousarray(bank, dtype=np.float32)
+    if not images and not np.isfinite(bank).all():
+        raise ValueError("gaussian_fit: the bank's embeddings must be finite")
+    if labels is None:
+        return np.zeros(N, np.int64), 1, float(shrink), bank, images, batch
+    y = np.asarray(labels)
+    if y.ndim == 2 and y.shape == (N, classes):
+        y = np.argmax(y, axis=1)
+    elif y.ndim != 1 or y.shape[0] != N or y.dtype.kind not in "iu":
+        raise ValueError("gaussian_fit: labels must be {0} integers or one-hot [{0}, {1}], got shape {2} of {3}"
+                         .format(N, classes, y.shape, y.dtype))
+    y = y.astype(np.int64)
+    if y.min() < 0 or y.max() >= classes:
+        raise ValueError("gaussian_fit: labels must lie in [0, {}]".format(classes - 1))
+    return y, int(classes), float(shrink), bank, images, batch
+
+
+def mahalanobis_check(stats, G, U, batch, backend):
+    """The validated ``(stats as arrays, C, batch)`` of a ``mahalanobis`` request, before any forward runs:
+    ``ValueError`` on a ``stats`` that lacks a key of ``GAUSS_KEYS``, whose shapes disagree with each other or
+    with the model's ``G`` members and ``U`` units, or whose ``whiten`` / ``wmean`` are not finite; a bad
+    ``batch`` or ``backend``."""
+    batch = embed_check(batch, backend)
+    try:
+        st = {k: np.asarray(stats[k]) for k in GAUSS_KEYS}
+    except (KeyError, TypeError, IndexError):
+        raise ValueError("mahalanobis: stats must be the dict gaussian_fit returns (keys {})".format(GAUSS_KEYS))
+    C = st["count"].shape[0] if st["count"].ndim == 1 else 0
+    want = {"mean": (G, C, U), "cov": (G, U, U), "whiten": (G, U, U), "wmean": (G, C, U)}
+    if C < 1 or any(st[k].shape != v for k, v in want.items()):
+        raise ValueError("mahalanobis: stats are not this model's ({} member(s) of {} units): shapes {}".format(
+            G, U, {k: st[k].shape for k in GAUSS_KEYS}))
+    if not (np.isfinite(st["whiten"]).all() and np.isfinite(st["wmean"]).all()):
+        raise ValueError("mahalanobis: stats hold values that are not finite")
+    st["whiten"] = np.ascontiguousarray(st["whiten"], np.float32)
+    st["wmean"] = np.ascontiguousarray(st["wmean"], np.float32)
+    return st, C, batch
+
+
+def gaussian_moments(f, labels, C):
+    """``(count int64 [C], mean fp32 [C, U], cov fp64 [U, U])`` of fp32 features ``f [N, U]``, the definition:
+    ``mean_c`` is the fp64 sum of the class's rows in row order over its count, rounded to fp32 (zeros for an
+    empty class); ``c_r = fp32(f_r - mean_{y_r})``, one fp32 subtraction per element; ``cov`` is the fp64 sum of
+    ``c_r c_r^T`` in row order (every product of two fp32 values is exact in fp64) divided by ``N``: symmetric to
+    the bit. One pass over the rows, one ``U x U`` update each: minutes for 60,000 x 500."""
+    f = np.asarray(f, np.float32)
+    N, U = f.shape
+    count = np.bincount(labels, minlength=C).astype(np.int64)
+    sums = np.zeros((C, U))
+    np.add.at(sums, labels, f.astype(np.float64))            # unbuffered: row order
+    mean = (sums / np.maximum(count, 1)[:, None]).astype(np.float32)
+    c = (f - mean[labels]).astype(np.float64)
+    acc = np.zeros((U, U))
+    for r in range(N):
+        acc += np.multiply.outer(c[r], c[r])
+    return count, mean, acc / N
+
+
+def gaussian_whiten(cov, mean, shrink):
+    """``(W fp32 [U, U], t fp32 [C, U])`` of one member: ``shrunk = (1 - shrink) cov + shrink (trace(cov) / U) I``,
+    ``shrunk = L L^T`` by fp64 Cholesky, ``W = fp32(L^-T)`` and ``t_c = fp32(W^T mean_c)`` in fp64 from the fp32
+    ``W``. ``ValueError`` naming ``shrink`` when ``shrunk`` is not positive definite."""
+    U = cov.shape[0]
+    shrunk = (1.0 - shrink) * cov + shrink * (np.trace(cov) / U) * np.eye(U)
+    try:
+        Li = np.linalg.inv(np.linalg.cholesky(shrunk))
+        if not np.isfinite(Li).all():
+            raise np.linalg.LinAlgError("not finite")
+    except np.linalg.LinAlgError:
+        raise ValueError("gaussian_fit: the covariance is singular at shrink={!r} (dead units or too few rows): "
+                         "pass a larger shrink".format(shrink))
+    W = np.ascontiguousarray(Li.T).astype(np.float32)
+    return W, (mean.astype(np.float64) @ W.astype(np.float64)).astype(np.float32)
+
+
+def gaussian_stats(count, mean, cov, shrink):
+    """The ``stats`` dict of ``gaussian_fit`` from the members' moments ``mean [G, C, U]``, ``cov [G, U, U]``."""
+    wt = [gaussian_whiten(cov[g], mean[g], shrink) for g in range(len(cov))]
+    return {"count": count, "mean": mean, "cov": cov, "whiten": np.stack([w for w, _ in wt]),
+            "wmean": np.stack([t for _, t in wt]), "shrink": np.float64(shrink)}
+
+
+def mahalanobis_distance(f, W, t, count, rows=4096):
+    """fp32 ``[n, C]`` squared distances of fp32 features ``f [n, U]`` of one member, the definition:
+    ``z = f W`` and ``d_c = sum_j (z_j - t_cj)^2`` in fp64 over the fp32 values, rounded to fp32 once; ``+inf``
+    for a class without rows."""
+    W64, t64 = np.asarray(W, np.float64), np.asarray(t, np.float64)
+    out = np.empty((f.shape[0], t64.shape[0]), np.float32)
+    for s in range(0, f.shape[0], rows):
+        z = np.asarray(f[s:s + rows], np.float64) @ W64
+        out[s:s + rows] = ((z[:, None, :] - t64[None]) ** 2).sum(-1)
+    out[:, np.asarray(count) == 0] = np.inf
+    return out
+
+
+def member_mean(d, weights):
+    """The weighted mean of the members' distances ``d [G, n, C]`` in member order with the rounding of the
+    ensemble's other means (``acc = w[0] * d[0]``, then ``acc = acc + w[g] * d[g]``, fp32)."""
+    w = np.asarray(weights, np.float32)
+    acc = w[0] * d[0]
+    for g in range(1, len(d)):
+        acc = acc + w[g] * d[g]
+    return acc.astype(np.float32)
+
+
+def gaussian_fit_run(model, members, bank, labels, shrink, device, batch, backend):
+    """``gaussian_fit`` of a classifier (``members = [model]``) or an ensemble."""
+    first, G, U = members[0], len(members), members[0].dense_units
+    labels, C, shrink, bank, images, batch = gaussian_check(labels, shrink, bank, first.input_shape, first.classes,
+                                                            G * U, batch, backend)
+    dev, backend = _nn_backend(device, backend)
+    if backend == "hip":
+        gaussian_check_hip(C)
+        pred = model.hip_predictor(dev, batch)
+        count, mean, cov = gaussian_state(pred, G).fit(pred, bank, images, labels, C)
+    else:
+        f = embed_torch(members, bank, dev, batch) if images else bank
+        mom = [gaussian_moments(f[:, g * U:(g + 1) * U], labels, C) for g in range(G)]
+        count, mean, cov = mom[0][0], np.stack([m[1] for m in mom]), np.stack([m[2] for m in mom])
+    return gaussian_stats(count, mean, cov, shrink)
+
+
+def mahalanobis_run(model, members, weights, x, stats, device, batch, backend):
+    """``mahalanobis`` of a classifier (``members = [model]``, weight 1) or an ensemble."""
+    first, G, U = members[0], len(members), members[0].dense_units
+    st, C, batch = mahalanobis_check(stats, G, U, batch, backend)
+    x = first._check_x(x)
+    dev, backend = _nn_backend(device, backend)
+    if backend == "hip":
+        gaussian_check_hip(C)
+        pred = model.hip_predictor(dev, batch)
+        d = gaussian_state(pred, G).distance(pred, x, st, C)
+    else:
+        f = embed_torch(members, x, dev, batch)
+        d = np.stack([mahalanobis_distance(f[:, g * U:(g + 1) * U], st["whiten"][g], st["wmean"][g], st["count"])
+                      for g in range(G)])
+    return member_mean(d, weights)
+
+
 def predict_batch(batch):
     """Rows per launch of the HIP predictor: ``batch`` rounded up to a multiple of 32, at least 32 and
     at most 256 (the cap of ``HipPopJob.eval_batch``)."""
@@ -1177,6 +1345,31 @@ class CnnClassifier(object):
         merge the results, or search it on the device. A bank row whose distance overflows to ``+inf`` is never
         returned by the device; a query with fewer than ``k`` finite distances gets ``(2^31 - 1, +inf)`` there."""
         return neighbors_run(self, [self], x, bank, k, metric, device, batch, backend)
+
+    def gaussian_fit(self, bank, labels=None, shrink=0.01, device=None, batch=256, backend=None):
+        """Class-conditional Gaussians with one tied covariance in the feature space of :meth:`embed` (Lee et al.,
+        2018), for :meth:`mahalanobis`. ``bank`` is images ``[N, H, W, C]`` or embeddings ``[N, dense_units]``
+        as in :meth:`neighbors`; ``labels`` an int array ``[N]`` in ``0..classes-1`` or one-hot ``[N, classes]``,
+        ``None`` for one Gaussian over the whole bank; ``shrink`` in ``[0, 1]`` blends the covariance with
+        ``trace / U`` times the identity. Returns a plain dict of numpy arrays (``np.savez`` keeps it; nothing goes
+        into model files): ``count`` int64 ``[C]``, ``mean`` fp32 ``[1, C, U]``, ``cov`` fp64 ``[1, U, U]`` (the
+        within-class scatter over ``N``, before shrinkage), ``whiten`` fp32 ``[1, U, U]`` (``W = L^-T`` of the
+        shrunk covariance ``L L^T``), ``wmean`` fp32 ``[1, C, U]`` (``W^T mean_c``) and ``shrink``. A singular
+        covariance (dead units at ``shrink=0``) is a ``ValueError`` that names ``shrink``.
+
+        The CPU or ``backend="torch"`` embeds by stock torch and runs the fp64 host definitions
+        (:func:`gaussian_moments`, :func:`gaussian_whiten`). A ``cuda`` device keeps the bank's hidden rows on the
+        device (at most 1 GiB, else a ``ValueError`` naming ``backend="torch"``) and forms the sums and the
+        scatter matrix there (csrc/hip/cnn_gaussian.hip): ``cov`` is within the split-fp32 bound of the
+        definition's at a reduction length of 1024 rows and does not depend on ``batch``; at most 16 classes."""
+        return gaussian_fit_run(self, [self], bank, labels, shrink, device, batch, backend)
+
+    def mahalanobis(self, x, stats, device=None, batch=256, backend=None):
+        """fp32 ``[n, C]``: the squared Mahalanobis distance of every image of ``x`` to every class Gaussian of
+        ``stats`` (:meth:`gaussian_fit`), ``+inf`` for a class without rows. ``d.min(1)`` is the
+        out-of-distribution score, ``d.argmin(1)`` the Gaussian-discriminant label. On a ``cuda`` device the
+        whitening product and the per-class sums run in one kernel (``gt_fs_dist``) at fp32 accuracy."""
+        return mahalanobis_run(self, [self], np.ones(1, np.float32), x, stats, device, batch, backend)
 
     def _torch_embed(self, x, dev, batch, dtype):
         """``embed`` by stock torch in ``dtype`` (fp32, or fp64: the tests' oracle): the chunks of
@@ -2006,6 +2199,123 @@ def neighbor_state(pred, G):
     return pred._nn
 
 
+def gaussian_check_hip(C):
+    """The ``ValueError`` of more classes than ``gt_fs_sums`` / ``gt_fs_dist`` take, before a predictor is built."""
+    from ..ops.cnn_kernels import FS_MAX_CLASSES
+    if C > FS_MAX_CLASSES:
+        raise ValueError("the HIP Gaussian kernels take at most {} classes, got {}; use backend=\"torch\"".format(
+            FS_MAX_CLASSES, C))
+
+
+def fs_store_rows(N, G, Up):
+    """Rows of the feature store of a fit of ``N`` rows, ``N`` rounded up to ``FS_ROW_PAD``; ``ValueError`` (before
+    any forward or allocation) when ``G x rows x Up`` fp32 values pass the launchers' 1 GiB."""
+    from ..ops.cnn_kernels import FS_MAX_STORE_BYTES, FS_ROW_PAD
+    Np = -(-N // FS_ROW_PAD) * FS_ROW_PAD
+    if G * Np * Up * 4 > FS_MAX_STORE_BYTES:
+        raise ValueError("gaussian_fit: {} rows x {} stored features take {:.2f} GiB on the device, above the HIP "
+                         "path's 1 GiB; use backend=\"torch\"".format(N, G * Up, G * Np * Up * 4.0 / 2 ** 30))
+    return Np
+
+
+class GaussianState(object):
+    """What a HIP predictor adds for ``gaussian_fit`` / ``mahalanobis``: the argument structs of
+    csrc/hip/cnn_gaussian.hip over the hidden rows of the predictor's :class:`NeighborState`, whose forward and
+    source view are used as they are. The feature store, the planes and the partials of a fit live for that
+    request only."""
+
+    PART_BYTES = 256 << 20       # fp32 scatter partials held at a time: the slices of one round
+
+    def __init__(self, pred, G):
+        self.nn = neighbor_state(pred, G)
+
+    def fit(self, pred, bank, images, labels, C):
+        """``(count int64 [C], mean fp32 [G, C, Ur], cov fp64 [G, Ur, Ur])`` of validated arguments: the bank's
+        hidden rows into the store (or the embeddings uploaded as they are), ``gt_fs_sums`` and the means on the
+        host, ``gt_fs_center``, then rounds of ``gt_fs_scatter`` + ``gt_fs_reduce``."""
+        K, L, dev, nn = pred.K, pred.job.L, pred.device, self.nn
+        G, Up, Ur, N = nn.G, nn.Up, nn.Ur, bank.shape[0]
+        Np = fs_store_rows(N, G, Up)
+        S = -(-N // K.FS_SLICE_ROWS)
+        count = np.bincount(labels, minlength=C).astype(np.int64)
+        with torch.cuda.device(dev):
+            src = K.NnSrc()
+            if images:
+                store = torch.empty((G, Np, Up), dtype=nn.hidden.dtype, device=dev)
+                for s0 in range(0, N, pred.EB):
+                    m = min(pred.EB, N - s0)
+                    nn.forward(pred, bank[s0:s0 + m])
+                    store[:, s0:s0 + m].copy_(nn.hidden[:, :m])
+                src.h, src.G, src.B, src.Up, src.Ur, src.flat, src.ld = store.data_ptr(), G, Np, Up, Ur, 0, 0
+                sprec = nn.prec
+            else:
+                store = torch.from_numpy(bank).to(dev)
+                src.h, src.G, src.B, src.Up, src.Ur, src.flat, src.ld = store.data_ptr(), G, N, Up, Ur, 1, G * Ur
+                sprec = 1
+            st = pred.job._stream()
+            lab = torch.from_numpy(labels.astype(np.int32)).to(dev)
+            part = torch.empty((S, G, C, Up), dtype=torch.float64, device=dev)
+            a = K.FsSumsArgs()
+            a.src, a.label, a.part, a.sprec, a.N, a.C = src, lab.data_ptr(), part.data_ptr(), sprec, N, C
+            K.check(L.gt_fs_sums(a, st), "fs_sums")
+            sums = np.zeros((G, C, Up))
+            for p in part.cpu().numpy():                     # slice order
+                sums += p
+            mean = (sums / np.maximum(count, 1)[None, :, None]).astype(np.float32)
+            mean_d = torch.from_numpy(mean).to(dev)
+            planes = torch.empty((3, G, Up, Np), dtype=torch.bfloat16, device=dev)
+            c = K.FsCenterArgs()
+            c.src, c.label, c.mean, c.planes = src, lab.data_ptr(), mean_d.data_ptr(), planes.data_ptr()
+            c.sprec, c.N, c.Np, c.C = sprec, N, Np, C
+            K.check(L.gt_fs_center(c, st), "fs_center")
+            slices = -(-Np // K.FS_SLICE_ROWS)
+            per = int(max(1, min(slices, self.PART_BYTES // (G * Up * Up * 4))))
+            buf = torch.empty((per, G, Up, Up), dtype=torch.float32, device=dev)
+            acc = torch.empty((G, Up, Up), dtype=torch.float64, device=dev)
+            t, r = K.FsScatterArgs(), K.FsReduceArgs()
+            t.planes, t.part, t.G, t.Up, t.Np = planes.data_ptr(), buf.data_ptr(), G, Up, Np
+            r.part, r.acc, r.G, r.Up = buf.data_ptr(), acc.data_ptr(), G, Up
+            for s0 in range(0, slices, per):
+                t.s0, t.ns = s0, min(per, slices - s0)
+                r.ns, r.first, r.last = t.ns, int(s0 == 0), int(s0 + t.ns == slices)
+                K.check(L.gt_fs_scatter(t, st), "fs_scatter")
+                K.check(L.gt_fs_reduce(r, st), "fs_reduce")
+            cov = acc[:, :Ur, :Ur].cpu().numpy() / N
+        return count, np.ascontiguousarray(mean[:, :, :Ur]), np.ascontiguousarray(cov)
+
+    def distance(self, pred, x, st, C):
+        """fp32 ``[G, n, C]`` of validated arguments: the planes of ``W^T`` and the whitened means once, then per
+        chunk of ``EB`` images the forward and ``gt_fs_dist`` into the request's result, read back once."""
+        K, L, dev, nn = pred.K, pred.job.L, pred.device, self.nn
+        G, Up, Ur, n = nn.G, nn.Up, nn.Ur, x.shape[0]
+        with torch.cuda.device(dev):
+            wt = torch.zeros((G, Up, Up), dtype=torch.float32, device=dev)
+            wt[:, :Ur, :Ur].copy_(torch.from_numpy(st["whiten"]).to(dev).transpose(1, 2))
+            planes = torch.empty((3, G, Up, Up), dtype=torch.bfloat16, device=dev)
+            for p in range(3):                               # the exact split of common.h: wt = p0 + p1 + p2
+                planes[p].copy_(wt)
+                wt -= planes[p].float()
+            tm = torch.zeros((G, C, Up), dtype=torch.float32, device=dev)
+            tm[:, :, :Ur].copy_(torch.from_numpy(st["wmean"]).to(dev))
+            out = torch.empty((G, n, C), dtype=torch.float32, device=dev)
+            a = K.FsDistArgs()
+            a.q, a.wt, a.wmean, a.out = nn._src(pred), planes.data_ptr(), tm.data_ptr(), out.data_ptr()
+            a.sprec, a.C, a.ldo = nn.prec, C, n
+            a.empty = int(sum(1 << c for c in range(C) if st["count"][c] == 0))
+            for s in range(0, n, pred.EB):
+                a.m, a.r0 = min(pred.EB, n - s), s
+                K.check(L.gt_fs_dist(a, nn.forward(pred, x[s:s + a.m])), "fs_dist")
+            return out.cpu().numpy()
+
+
+def gaussian_state(pred, G):
+    """The cached :class:`GaussianState` of a predictor (its ``_gauss``), built on the first request."""
+    if pred._gauss is None:
+        with torch.cuda.device(pred.device):
+            pred._gauss = GaussianState(pred, G)
+    return pred._gauss
+
+
 def saliency_info(res, method):
     """The ``return_info`` dict of ``(map, target, base, baseline_score)``."""
     info = {"target": res[1], "base": res[2]}
@@ -2353,6 +2663,7 @@ class HipPredictor(object):
         self._mc = None              # McState, created on the first Monte-Carlo dropout request
         self._sal = None             # SaliencyState, created on the first saliency request
         self._nn = None              # NeighborState, created on the first embed / neighbors request
+        self._gauss = None           # GaussianState, created on the first gaussian_fit / mahalanobis request
 
     def forward(self):
         """The launches of one chunk on the current stream: staging tensor -> ``logits`` / ``proba``."""

@@ -363,6 +363,40 @@ class NnMergeArgs(C.Structure):
     _fields_ = [("cand_d", P), ("cand_i", P), ("out_d", P), ("out_i", P), ("m", I), ("S", I), ("k", I)]
 
 
+FS_SLICE_ROWS = 1024    # rows of one fp32 partial of the scatter (csrc/hip/cnn_gaussian.hip FS_SLICE_ROWS)
+FS_ROW_PAD = 64         # the stored rows of a Gaussian fit are padded to this (FS_ROW_PAD)
+FS_MAX_CLASSES = 16     # FS_MAXC
+FS_MAX_STORE_BYTES = 1 << 30
+FS_MAX_PART_BYTES = 1 << 30
+
+
+class FsSumsArgs(C.Structure):
+    """csrc/hip/cnn_gaussian.hip FsSumsArgs: per-class fp64 column sums per slice of rows (gt_fs_sums)."""
+    _fields_ = [("src", NnSrc), ("label", P), ("part", P), ("sprec", I), ("N", I), ("C", I)]
+
+
+class FsCenterArgs(C.Structure):
+    """csrc/hip/cnn_gaussian.hip FsCenterArgs: centred rows -> feature-major bf16 planes (gt_fs_center)."""
+    _fields_ = [("src", NnSrc), ("label", P), ("mean", P), ("planes", P), ("sprec", I), ("N", I), ("Np", I),
+                ("C", I)]
+
+
+class FsScatterArgs(C.Structure):
+    """csrc/hip/cnn_gaussian.hip FsScatterArgs: planes -> one fp32 scatter partial per slice (gt_fs_scatter)."""
+    _fields_ = [("planes", P), ("part", P), ("G", I), ("Up", I), ("Np", I), ("s0", I), ("ns", I)]
+
+
+class FsReduceArgs(C.Structure):
+    """csrc/hip/cnn_gaussian.hip FsReduceArgs: a round of partials into the fp64 matrix (gt_fs_reduce)."""
+    _fields_ = [("part", P), ("acc", P), ("G", I), ("Up", I), ("ns", I), ("first", I), ("last", I)]
+
+
+class FsDistArgs(C.Structure):
+    """csrc/hip/cnn_gaussian.hip FsDistArgs: hidden rows -> squared Mahalanobis distances (gt_fs_dist)."""
+    _fields_ = [("q", NnSrc), ("wt", P), ("wmean", P), ("out", P), ("sprec", I), ("m", I), ("C", I), ("empty", I),
+                ("r0", I), ("ldo", I)]
+
+
 class DenseDgradArgs(C.Structure):
     _fields_ = [("dH", P), ("wt", P), ("dx", P), ("G", I), ("B", I), ("Fp", I), ("Up", I), ("prec", I),
                 ("wps", C.c_long), ("unpool_mask", P), ("unpool_x0", P), ("unpool_x1", P), ("unpool_sel", P),
@@ -574,6 +608,18 @@ def lib():
         assert L.gt_nn_max_k() == NN_MAX_K, "NN_MAX_K mismatch"
         assert L.gt_nn_max_slices() == NN_MAX_SLICES, "NN_MAX_SLICES mismatch"
         assert L.gt_nn_bank_tile() == NN_BANK_TILE, "NN_BANK_TILE mismatch"
+        for fname, sname, st in (("gt_fs_sums", "fs_sums", FsSumsArgs), ("gt_fs_center", "fs_center", FsCenterArgs),
+                                 ("gt_fs_scatter", "fs_scatter", FsScatterArgs),
+                                 ("gt_fs_reduce", "fs_reduce", FsReduceArgs), ("gt_fs_dist", "fs_dist", FsDistArgs)):
+            fn = getattr(L, fname)
+            fn.argtypes = [C.POINTER(st), P]
+            fn.restype = I
+            size = getattr(L, "gt_sizeof_{}_args".format(sname))
+            size.restype = C.c_size_t
+            assert size() == C.sizeof(st), st.__name__ + " ABI mismatch"
+        assert L.gt_fs_slice_rows() == FS_SLICE_ROWS, "FS_SLICE_ROWS mismatch"
+        assert L.gt_fs_row_pad() == FS_ROW_PAD, "FS_ROW_PAD mismatch"
+        assert L.gt_fs_max_classes() == FS_MAX_CLASSES, "FS_MAX_CLASSES mismatch"
         assert L.gt_rise_max_masks() == RISE_MAX_MASKS, "RISE_MAX_MASKS mismatch"
         assert L.gt_rise_max_cells() == RISE_MAX_CELLS, "RISE_MAX_CELLS mismatch"
         L.gt_adam_segments.argtypes = [C.POINTER(AdamArgs), I, P]

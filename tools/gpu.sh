@@ -27,6 +27,7 @@
 #   bash tools/gpu.sh cnn-saliency            saliency(): masked forward + backward chain + gt_conv_in_dgrad vs plain HIP predict (the floor) vs the stock-torch backend, integrated gradients on IG_ROWS rows, classifier and k-ensemble; the kernels' device time by a kernel trace run of its own (ROWS= IG_ROWS= STEPS= FIT_ROWS= K= REPS= OUT= TIME=)
 #   bash tools/gpu.sh cnn-mc                predict_mc(): forward + gt_head_mc vs plain HIP predict (the floor) vs the stock-torch backend, classifier and k-ensemble; the kernel's device time by a kernel trace run of its own (ROWS= SAMPLES= FIT_ROWS= K= REPS= OUT= TIME=)
 #   bash tools/gpu.sh cnn-neighbors         neighbors(): forwards + gt_nn_bank / gt_nn_topk / gt_nn_merge vs HIP embed + torch.cdist + topk vs HIP embed + a host search, classifier and k-ensemble; the kernels' device time by a kernel trace run of its own (ROWS= BANK= K= FIT_ROWS= MEMBERS= REPS= OUT= TIME=)
+#   bash tools/gpu.sh cnn-gaussian          gaussian_fit() + mahalanobis(): forwards + gt_fs_* vs HIP embed + torch fp32 (Xc.T @ Xc, cdist) vs HIP embed + fp64 BLAS on the host; the kernels' device time by a kernel trace run of its own (ROWS= BANK= FIT_ROWS= REPS= OUT= TIME=)
 #   bash tools/gpu.sh rehearse                2-rank torchrun bench on one GPU (gloo control plane)
 #   bash tools/gpu.sh secondary               bench lines: reference fold semantics, torch comparator
 #
@@ -298,6 +299,20 @@ cnn-neighbors)
     --fit-rows ${FIT_ROWS:-2000} --members ${MEMBERS:-4} ${NN_ARGS:-} > $out/prof.log 2>&1 &&
   find /tmp/prof_nn -name "*kernel_stats.csv" -exec cp {} $out/kernel_stats.csv \; &&
   grep -E "Name|nn_topk|nn_bank|nn_merge|dense_fwd" $out/kernel_stats.csv | cut -c1-300; rc=$?
+  [ $rc -eq 0 ] || { tail -5 $out/bench.err $out/prof.log 2>/dev/null; cut -c1-2000 $out/bench.json; }
+  exit $rc ;;
+cnn-gaussian)
+  # the result line, then the kernels' own durations from a kernel trace of one child run of its own (a fit, then
+  # two gaussian_fit + mahalanobis calls); the files are kept under $OUT
+  out=${OUT:-/tmp/cnn_gaussian}; heartbeat; mkdir -p $out; rocprof_env; rm -rf /tmp/prof_fs
+  timeout -k 10 ${TIME:-600} python -u tools/bench_cnn_gaussian.py --rows ${ROWS:-10000} --bank ${BANK:-50000} \
+    --fit-rows ${FIT_ROWS:-2000} --reps ${REPS:-5} ${FS_ARGS:-} > $out/bench.json 2> $out/bench.err &&
+  tail -1 $out/bench.json | cut -c1-8000 &&
+  timeout -k 10 300 rocprofv3 --kernel-trace --stats -d /tmp/prof_fs -o run --output-format csv -- \
+    python3 tools/bench_cnn_gaussian.py --trace --rows ${ROWS:-10000} --bank ${BANK:-50000} \
+    --fit-rows ${FIT_ROWS:-2000} ${FS_ARGS:-} > $out/prof.log 2>&1 &&
+  find /tmp/prof_fs -name "*kernel_stats.csv" -exec cp {} $out/kernel_stats.csv \; &&
+  grep -E "Name|fs_|dense_fwd" $out/kernel_stats.csv | cut -c1-300; rc=$?
   [ $rc -eq 0 ] || { tail -5 $out/bench.err $out/prof.log 2>/dev/null; cut -c1-2000 $out/bench.json; }
   exit $rc ;;
 cnn-saliency)
